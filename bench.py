@@ -10,7 +10,10 @@ index), no input scatter) and ONE RCCL all-gather of a packed (B, P + 4)
 buffer (parameters + the 4 status words, bit-cast) joins them on every rank
 (config C4 at N = 8: 65536 problems).
 
-Prints ONE JSON line on rank 0 with the metric plus:
+A plain run (no --full) does only what the headline figure needs: it sets up,
+warms up, times the --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints ONE JSON line on rank 0 with the metric,
+`ms_per_step` (the milliseconds one timed step took) and:
   roofline     -- the solve kernel's algorithmic HBM bytes per launch (compact
                   byte model, stated in `byte_model`; the dense 8P^2 model's
                   equivalent rate beside it) over its HIP-event-timed average
@@ -18,13 +21,16 @@ Prints ONE JSON line on rank 0 with the metric plus:
                   figure for this exact configuration from the committed summary
                   (profiles/pmc_traffic.json, source tag in `traffic_source`),
                   else null.
+With --full the line also carries everything that takes runs of its own, all
+after the timed region: live rocprofv3 counter passes and the history-stream
+ceiling under `roofline`, the `sustained` phase, and
   cpu_baseline -- the CPU oracle (PyTorch-CPU restatement of the reference,
                   bitwise-equal to it) on a bounded sample of the same workload:
                   1 warm-up, then 3 timed runs on 3 disjoint slices, median rate;
                   rank 0 at N = 1 only.
   parity       -- the GPU result for those same sampled problems against the
                   oracle's: per-problem normwise relative error distribution.
-Launch: python bench.py [--gpus N --steps K --warmup W]
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
         N > 1 without WORLD_SIZE in the environment: this process starts N ranks
         itself (python -m torch.distributed.run, one rank per GPU, RCCL backend)
         before touching the GPU and exits with their status.
@@ -36,6 +42,7 @@ import socket
 import statistics
 import subprocess
 import sys
+import tempfile
 import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
@@ -96,6 +103,17 @@ def parse(argv=None):
                    help="after the timed region, keep solving the same batch for about this long (same step, no "
                         "collective) and report the sustained rate beside the timed one (clocks and power at "
                         "steady state; a phase long enough for a GPU-busy sampler to see).  0 = skip")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also run everything beside the headline figure: the CPU-oracle "
+                        "baseline and the parity blocks (--cpu-sample, --parity-envelope, --no-converged-parity), "
+                        "the live counter passes and the history-stream ceiling (--no-live-counters), the sustained "
+                        "phase (--sustain-seconds), the golden / spot-check comparisons.  Without it those options "
+                        "have no effect and their blocks are null or absent")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned (x, status; the gradients "
+                        "with --differentiate; the gathered batch at N > 1) as DIR/<name>.npy, float32 / float64, "
+                        "at most 64 MB in all (beyond that a fixed seeded sample of rows, listed in "
+                        "DIR/<name>_rows.npy)")
     p.add_argument("--launch-test", action="store_true",
                    help="multi-rank LAUNCH plumbing check on CPU (gloo, identity stub instead of the solve); "
                         "prints a line marked as a launch test, never a measurement")
@@ -344,20 +362,78 @@ def converged_parity(args, x0, obs, vis, closure, n_env, dev):
             "mean_iterations": float(st[:, 0].double().mean())}
 
 
-def _scenes(args, b, first, distortion, ray):
+SCENE_CACHE_DIR = tempfile.gettempdir()
+
+
+def _scene_chunk(job):
     from deep_attention_visual_odometry_amd import make_scenes
 
-    cache = f"/tmp/dava_scenes_{args.seed}_{first}_{b}_{args.views}_{args.points}_{int(distortion)}_{int(ray)}.npz"
-    if os.path.exists(cache):  # generation is ~1 ms/problem on the host; cache it for repeated runs
-        z = np.load(cache)
-        return z["initial"], z["observations"], z["visibility"]
-    s = make_scenes(b, args.views, args.points, distortion=distortion, seed=args.seed, first_index=first,
-                    ray_angle=ray)
-    try:
-        np.savez(cache, initial=s.initial, observations=s.observations, visibility=s.visibility)
-    except OSError:
-        pass
+    n, views, points, distortion, seed, first, ray = job
+    s = make_scenes(n, views, points, distortion=distortion, seed=seed, first_index=first, ray_angle=ray)
     return s.initial, s.observations, s.visibility
+
+
+def _scenes(args, b, first, distortion, ray, workers=1):
+    """This rank's problems: a pure function of (seed, global index), so the inputs are the same from run to
+    run.  workers > 1 generates contiguous chunks in forked worker processes (same values: every problem has
+    its own generator) -- only in a process that has not initialised the GPU yet."""
+    cache = os.path.join(SCENE_CACHE_DIR, f"dava_scenes_{args.seed}_{first}_{b}_{args.views}_{args.points}_"
+                                          f"{int(distortion)}_{int(ray)}.npz")
+    if os.path.exists(cache):  # generation is ~1 ms/problem on the host; cache it for repeated runs
+        try:
+            z = np.load(cache)
+            return z["initial"], z["observations"], z["visibility"]
+        except (OSError, ValueError, KeyError, EOFError):
+            pass  # unreadable cache: generate again
+    workers = 1 if torch.cuda.is_initialized() else max(1, min(workers, b // 256))  # never fork a GPU process
+    bounds = [b * i // workers for i in range(workers + 1)]
+    jobs = [(hi - lo, args.views, args.points, distortion, args.seed, first + lo, ray)
+            for lo, hi in zip(bounds[:-1], bounds[1:])]
+    if workers > 1:
+        import multiprocessing
+        from concurrent.futures import ProcessPoolExecutor
+
+        with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("fork")) as pool:
+            parts = list(pool.map(_scene_chunk, jobs))
+    else:
+        parts = [_scene_chunk(j) for j in jobs]
+    initial, observations, visibility = (np.concatenate([part[i] for part in parts]) for i in range(3))
+    tmp = f"{cache}.{os.getpid()}.tmp.npz"
+    try:  # written under a private name and renamed, so a reader never sees half a file
+        np.savez(tmp, initial=initial, observations=observations, visibility=visibility)
+        os.replace(tmp, cache)
+    except OSError:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return initial, observations, visibility
+
+
+DUMP_CAP_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 20251015
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> tensor, first axis = problems) as path/<name>.npy.  Floating point
+    stays float32 / float64, anything else (the int32 status words) becomes float64, which holds it exactly.
+    Above DUMP_CAP_BYTES in all, every array keeps a fixed seeded sample of its rows (ascending; the row
+    numbers go to path/<name>_rows.npy), its share of the cap in proportion to its size."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        out[name] = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    total = sum(a.nbytes for a in out.values())
+    written = {}
+    for name, a in out.items():
+        if total > DUMP_CAP_BYTES:
+            row_bytes = a.nbytes // max(a.shape[0], 1) + 8  # + its entry in <name>_rows.npy
+            rows = min(a.shape[0], max(1, int(DUMP_CAP_BYTES * (a.nbytes / total) // row_bytes) - 1))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=rows, replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "of_rows": int(out[name].shape[0])}
+    return written
 
 
 def main():
@@ -370,6 +446,9 @@ def main():
     if world != args.gpus and rank == 0:
         print(f"bench.py: WORLD_SIZE={world} but --gpus {args.gpus}; measuring {world} ranks", file=sys.stderr)
     launch_test = args.launch_test
+    if not args.full:  # a plain run: set up, warm up, time the steps, dump, print
+        args.cpu_sample, args.sustain_seconds = 0, 0.0
+        args.no_live_counters, args.converged_parity = True, False
     if launch_test:
         dev = torch.device("cpu")
         if world > 1:
@@ -388,7 +467,12 @@ def main():
         raise SystemExit("--residual ray_angle is pinhole only: add --no-distortion")
     b = args.batch
     first = shard_range(world * b, world, rank).start  # this rank's slab of the global batch
-    x0_np, obs_np, vis_np = _scenes(args, b, first, distortion, ray)
+    # one rank: nothing has touched the GPU yet, so the scenes may come from forked workers
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    x0_np, obs_np, vis_np = _scenes(args, b, first, distortion, ray, workers=min(8, cpus) if world == 1 else 1)
     x0_cpu = torch.tensor(x0_np)
     obs_cpu = torch.tensor(obs_np)
     vis_cpu = torch.tensor(vis_np)
@@ -522,6 +606,11 @@ def main():
         elapsed = t.item()
     ranks = per_rank_phases(kernel_ms, gather_ms, world, dev) if world > 1 else None
     peak_bytes = None if launch_test else int(torch.cuda.max_memory_allocated(dev))
+    if args.dump_outputs and rank == 0:  # the last timed step's results, before anything else runs
+        outputs = {"x": gathered[0], "status": gathered[1]} if gathered is not None else {"x": x, "status": status}
+        if args.differentiate and not launch_test:
+            outputs.update({"grad_x0": solve.grads[0], "grad_observations": solve.grads[1]})
+        dump_outputs(args.dump_outputs, outputs)
     sustained = None
     if args.sustain_seconds > 0 and not launch_test and not args.differentiate and args.entry != "closure":
         sustained = sustain(args, solve, sync, elapsed / args.steps, world, b, dev)
@@ -566,7 +655,8 @@ def main():
                 line["sustained"] = sustained
             if world > 1:
                 line["per_rank"] = ranks
-                line["spot_check"] = spot_check(args, x0_cpu, obs_cpu, vis_cpu, x_all, distortion, ray)
+                if args.full:
+                    line["spot_check"] = spot_check(args, x0_cpu, obs_cpu, vis_cpu, x_all, distortion, ray)
             print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
@@ -909,7 +999,7 @@ def measurement_line(args, line, world, b, p, mn, distortion, ray, plan, kernel_
                         "algorithmic saving, not skipped work"}
     cpu, parity = (cpu_baseline(args, x0_cpu, obs_cpu, vis_cpu, x) if (world == 1 and args.cpu_sample > 0)
                    else (None, None))
-    if parity is None and fixed_k:
+    if parity is None and fixed_k and args.full:
         parity = golden_parity(args, x0_cpu, x)
     if roofline is not None and world == 1 and not args.no_live_counters:
         measured, detail = live_traffic(args)

@@ -38,6 +38,7 @@ for s in "$@"; do
         || { tail -5 gpurun_out/smoke.log; exit 1; }
       tail -1 gpurun_out/smoke.log ;;
     bench)
+      val="--full $val"  # the whole line: CPU baseline, parity blocks, live counters, sustained phase
       step bench "$val"
       timeout -k 10 500 python3 bench.py ${val} > gpurun_out/bench.log 2>&1 || { tail -5 gpurun_out/bench.log; exit 1; }
       tail -1 gpurun_out/bench.log | cut -c1-600 ;;
