@@ -57,14 +57,6 @@ __device__ unsigned long long g_eval_cycles[kEvalSections];
 // per-(view, point) arithmetic on v_pk_{fma,mul,add}_f32, two points per instruction.
 typedef float pf2 __attribute__((ext_vector_type(2)));
 
-struct Layout {
-  int M, N, P, distort;
-  __device__ __forceinline__ int pt(int n) const { return 3 + 3 * n; }
-  __device__ __forceinline__ int tr(int m) const { return 3 + 3 * N + 3 * (m - 1); }
-  __device__ __forceinline__ int rot(int m) const { return 3 + 3 * N + 3 * (M - 1) + 3 * (m - 1); }
-  __device__ __forceinline__ int dist() const { return 3 + 3 * N + 6 * (M - 1); }
-};
-
 // ---- Taylor-branched ratios, same thresholds and series as the reference ----
 // (templated on the scalar: float, or Dual for second derivatives, dava_dual.hpp)
 // sx, cx: sin x and cos x, computed once by the caller (sincos_)

@@ -80,23 +80,9 @@ __global__ __launch_bounds__(kBlock) void ba_second_order_kernel(SecondArgs a) {
   }
 }
 
-static int second_check(const DavaScene* s) {
-  if (!s) return DAVA_ERR_INVALID_ARGUMENT;
-  if (s->batch < 0 || s->num_views < 2 || s->num_points < 1) return DAVA_ERR_INVALID_ARGUMENT;
-  const int P = 3 + 3 * s->num_points + 6 * (s->num_views - 1) + (s->distortion ? 5 : 0);
-  if (s->num_parameters != P) return DAVA_ERR_INVALID_ARGUMENT;
-  if (s->batch > 0 && (!s->observations || !s->visibility)) return DAVA_ERR_INVALID_ARGUMENT;
-  if (s->residual != DAVA_RESIDUAL_SQUARED_REPROJECTION && s->residual != DAVA_RESIDUAL_RAY_ANGLE)
-    return DAVA_ERR_INVALID_ARGUMENT;
-  if (s->residual == DAVA_RESIDUAL_RAY_ANGLE && s->distortion) return DAVA_ERR_UNSUPPORTED;
-  return DAVA_OK;
-}
-
 template <int RES>
 static void launch_second(const SecondArgs& a, int B, int lds, hipStream_t s) {
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ba_second_order_kernel<RES>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  set_dynamic_lds(ba_second_order_kernel<RES>, lds);
   hipLaunchKernelGGL(ba_second_order_kernel<RES>, dim3(B), dim3(kBlock), lds, s, a);
 }
 
@@ -114,7 +100,7 @@ extern "C" int dava_ba_second_order(const DavaScene* scene, const float* x, cons
 extern "C" int dava_ba_second_order_obs(const DavaScene* scene, const float* x, const float* direction,
                                         const float* obs_direction, float* error_out, float* grad_out, float* hv_out,
                                         float* obs_grad_out, float* obs_hv_out, void* stream) {
-  const int st = second_check(scene);
+  const int st = check_scene(scene, true);
   if (st != DAVA_OK) return st;
   if (scene->batch == 0) return DAVA_OK;
   if (!x) return DAVA_ERR_INVALID_ARGUMENT;
@@ -122,7 +108,7 @@ extern "C" int dava_ba_second_order_obs(const DavaScene* scene, const float* x, 
   const int lds = carve_second(scene->num_views, scene->num_points, Pv).total_bytes;
   if (lds > 160 * 1024) return DAVA_ERR_UNSUPPORTED;
   SecondArgs a;
-  a.L = Layout{scene->num_views, scene->num_points, scene->num_parameters, scene->distortion ? 1 : 0};
+  a.L = make_layout(scene);
   a.Pv = Pv;
   a.obs = scene->observations;
   a.vis = scene->visibility;

@@ -670,8 +670,7 @@ template <int RES>
 static void launch_adjoint(const AdjointArgs& a, int B, int lds, int gm, int gt, int nw, hipStream_t s) {
   if (gt == 0 && a.sc_global) {  // LDS mode, the tape's scalar row in place
     auto go = [&](auto kernel) {
-      if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      set_dynamic_lds(kernel, lds);
       hipLaunchKernelGGL(kernel, dim3(B), dim3(kAdjBlock), lds, s, a);
     };
     if (gm <= 1) go(bfgs_ba_adjoint_kernel<RES, 1, 0, kAdjWaves, true>);
@@ -681,8 +680,7 @@ static void launch_adjoint(const AdjointArgs& a, int B, int lds, int gm, int gt,
     return;
   }
   auto go = [&](auto kernel, int threads) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    set_dynamic_lds(kernel, lds);
     hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), lds, s, a);
   };
   if (gt > 0 && nw == 8) {  // global-vector mode, eight waves: 4 or 7 float4 groups per thread
@@ -707,13 +705,10 @@ static bool adjoint_gv(const DavaScene* s, const TapeLayout& tl) {
 static int adjoint_groups(const TapeLayout& tl) { return (tl.Pv / 4 + kAdjBlock - 1) / kAdjBlock; }
 
 static int adjoint_check(const DavaScene* s, const DavaSolverConfig* c) {
-  if (!s || !c) return DAVA_ERR_INVALID_ARGUMENT;
-  if (s->batch < 0 || s->num_views < 2 || s->num_points < 1) return DAVA_ERR_INVALID_ARGUMENT;
-  const int P = 3 + 3 * s->num_points + 6 * (s->num_views - 1) + (s->distortion ? 5 : 0);
-  if (s->num_parameters != P) return DAVA_ERR_INVALID_ARGUMENT;
-  if (s->residual != DAVA_RESIDUAL_SQUARED_REPROJECTION && s->residual != DAVA_RESIDUAL_RAY_ANGLE)
-    return DAVA_ERR_INVALID_ARGUMENT;
-  if (s->residual == DAVA_RESIDUAL_RAY_ANGLE && s->distortion) return DAVA_ERR_UNSUPPORTED;
+  if (!c) return DAVA_ERR_INVALID_ARGUMENT;
+  const int st = check_scene(s, false);  // (the launch checks the data pointers itself)
+  if (st != DAVA_OK) return st;
+  const int P = s->num_parameters;
   if (c->hessian_mode != DAVA_HESSIAN_COMPACT || c->iterations < 1 || c->iterations > 1025) return DAVA_ERR_UNSUPPORTED;
   const TapeLayout tl = tape_layout(s->batch, P, c->iterations);
   if (adjoint_gv(s, tl)) {
@@ -786,7 +781,7 @@ extern "C" int dava_ba_solve_backward(const DavaScene* scene, const DavaSolverCo
   if (!workspace || workspace_bytes < rows + gvb) return DAVA_ERR_WORKSPACE;
   const bool gv = adjoint_gv(scene, tl);
   AdjointArgs a;
-  a.L = Layout{scene->num_views, scene->num_points, scene->num_parameters, scene->distortion ? 1 : 0};
+  a.L = make_layout(scene);
   a.Pv = tl.Pv;
   a.K = tl.K;
   a.tl = tl;

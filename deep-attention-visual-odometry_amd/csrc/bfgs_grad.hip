@@ -205,9 +205,7 @@ int update_backward(int64_t batch, int64_t n, const T* h, const T* s, const T* y
   if (!h || !s || !y || !g) return DAVA_ERR_INVALID_ARGUMENT;
   const size_t lds = kUpdateBackwardVectors * (size_t)n * sizeof(T);
   if (lds > 150 * 1024) return DAVA_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(update_backward_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_dynamic_lds(update_backward_kernel<T>, (int)lds);
   hipLaunchKernelGGL(update_backward_kernel<T>, dim3((unsigned)batch), dim3(kBlock), lds,
                      static_cast<hipStream_t>(stream), n, h, s, y, g, gh, gs, gy);
   return launched_ok();

@@ -246,9 +246,7 @@ int compact_direction(int64_t n_active, int64_t P, int64_t Pv, int64_t cap, int6
   const size_t lds = (2 * (size_t)Pv + 4 * (size_t)count) * sizeof(T);
   if (lds > 150 * 1024) return DAVA_ERR_UNSUPPORTED;
   const auto kernel = compact_direction_kernel<T>;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
+  set_dynamic_lds(kernel, (int)lds);
   hipLaunchKernelGGL(kernel, dim3((unsigned)n_active), dim3(kBlock), lds, static_cast<hipStream_t>(stream), P, Pv,
                      cap, count, idx, g, y, s, S, W, rho, c, gamma, d);
   return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
@@ -335,9 +333,7 @@ int update_inverse_hessian(int64_t batch, int64_t n, const T* h, const T* s, con
   if (!h || !s || !y || !out || out == h) return DAVA_ERR_INVALID_ARGUMENT;
   const size_t lds = 2 * (size_t)n * sizeof(T);
   if (lds > 150 * 1024) return DAVA_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(update_inverse_hessian_kernel<T>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_dynamic_lds(update_inverse_hessian_kernel<T>, (int)lds);
   hipLaunchKernelGGL(update_inverse_hessian_kernel<T>, dim3((unsigned)batch), dim3(kBlock), lds,
                      static_cast<hipStream_t>(stream), n, h, s, y, out);
   return launched();

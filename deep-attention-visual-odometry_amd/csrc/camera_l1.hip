@@ -352,9 +352,7 @@ int l1_camera_vjp(int64_t batch, int32_t estimates, int32_t views, int32_t point
   if (batch * estimates * D > 0x7fffffff) return DAVA_ERR_UNSUPPORTED;
   const size_t lds = grad_cot ? (size_t)views * points * 4 * sizeof(LDual<T>) : 0;
   if (lds > 150 * 1024) return DAVA_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(l1_camera_vjp_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_dynamic_lds(l1_camera_vjp_kernel<T>, (int)lds);
   const L1Args<T> a = l1_args(estimates, views, points, focal, cx, cy, trans, lie, world, target, vis, min_z,
                               pixel_ratio, max_grad, scale);
   hipLaunchKernelGGL(l1_camera_vjp_kernel<T>, dim3((unsigned)(batch * estimates * D)), dim3(kBlock), lds,
@@ -373,9 +371,7 @@ int l1_camera_evaluate(int64_t batch, int32_t estimates, int32_t views, int32_t 
   if (!err && !grad) return DAVA_OK;
   const size_t lds = grad ? (size_t)views * points * 4 * sizeof(T) : 0;
   if (lds > 150 * 1024) return DAVA_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(l1_camera_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_dynamic_lds(l1_camera_kernel<T>, (int)lds);
   L1Args<T> a = l1_args(estimates, views, points, focal, cx, cy, trans, lie, world, target, vis, min_z, pixel_ratio,
                         max_grad, scale);
   a.err = err; a.grad = grad;

@@ -14,6 +14,42 @@ constexpr int kWaves = kBlock / kWave;
 
 __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// The parameter vector of one problem: [intrinsics (3) | points (3 N) | translations, then rotations of
+// views 1 .. M-1 (3 each) | distortion (5, if any)].
+struct Layout {
+  int M, N, P, distort;
+  __device__ __forceinline__ int pt(int n) const { return 3 + 3 * n; }
+  __device__ __forceinline__ int tr(int m) const { return 3 + 3 * N + 3 * (m - 1); }
+  __device__ __forceinline__ int rot(int m) const { return 3 + 3 * N + 3 * (M - 1) + 3 * (m - 1); }
+  __device__ __forceinline__ int dist() const { return 3 + 3 * N + 6 * (M - 1); }
+};
+
+// ---- host helpers shared by the entry points ----
+// What every entry point that takes a scene checks first (need_data: the observations and visibility
+// pointers too; the size queries run without them).  Callers add their own limits after it.
+inline int check_scene(const DavaScene* s, bool need_data) {
+  if (!s) return DAVA_ERR_INVALID_ARGUMENT;
+  if (s->batch < 0 || s->num_views < 2 || s->num_points < 1) return DAVA_ERR_INVALID_ARGUMENT;
+  const int P = 3 + 3 * s->num_points + 6 * (s->num_views - 1) + (s->distortion ? 5 : 0);
+  if (s->num_parameters != P) return DAVA_ERR_INVALID_ARGUMENT;
+  if (need_data && s->batch > 0 && (!s->observations || !s->visibility)) return DAVA_ERR_INVALID_ARGUMENT;
+  if (s->residual != DAVA_RESIDUAL_SQUARED_REPROJECTION && s->residual != DAVA_RESIDUAL_RAY_ANGLE)
+    return DAVA_ERR_INVALID_ARGUMENT;
+  if (s->residual == DAVA_RESIDUAL_RAY_ANGLE && s->distortion) return DAVA_ERR_UNSUPPORTED;
+  return DAVA_OK;
+}
+
+inline Layout make_layout(const DavaScene* s) {
+  return Layout{s->num_views, s->num_points, s->num_parameters, s->distortion ? 1 : 0};
+}
+
+// A launch with more than 64 KiB of dynamic LDS has to raise the kernel's limit first.
+template <typename Kernel>
+inline void set_dynamic_lds(Kernel kernel, int bytes) {
+  if (bytes > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
 // torch.clamp(min=lo) semantics: NaN propagates (fmaxf would swallow it).
 template <typename T>
 __device__ __forceinline__ T clamp_min(T v, T lo) { return v < lo ? lo : v; }

@@ -223,7 +223,7 @@ class BFGSSolver(Module):
         self.last_status = status
         return x.reshape(parameters.shape)
 
-    MAX_COMPACT_ENTRIES = 1024  # kMaxCompactEntries in csrc/bfgs_solve.hip
+    MAX_COMPACT_ENTRIES = 1024  # kMaxCompactEntries in csrc/solve_plan.hpp
 
     def _resolve_mode(self, num_iterations: int, p: int, batch: int = 1, device=None) -> int:
         """'auto': the compact history (exact BFGS in product form, O(k P) bytes at iteration k)
@@ -237,7 +237,7 @@ class BFGSSolver(Module):
         at a higher fraction of the HBM peak than the dense sweep.
         Past 1025 iterations compact keeps its first 1024 updates as history and a problem still
         running at iteration 1025 folds them into the dense matrix and continues dense (the kernel's
-        HYBRID form, csrc/bfgs_solve.hip fold_history): its workspace is the history plus the dense
+        HYBRID form, csrc/solve_passes.hpp fold_history): its workspace is the history plus the dense
         matrices, so 'auto' takes it while that fits and the dense mode otherwise."""
         if self.hessian_mode == "dense":
             return _native.DAVA_HESSIAN_DENSE

@@ -1,4 +1,4 @@
-"""COMPACT past its history capacity: the HYBRID solve (csrc/bfgs_solve.hip fold_history).
+"""COMPACT past its history capacity: the HYBRID solve (csrc/solve_passes.hpp fold_history).
 
 COMPACT keeps one history entry per BFGS update, at most 1024; a problem still running at iteration
 1025 folds the history into the dense inverse Hessian once and continues with the dense sweep (the

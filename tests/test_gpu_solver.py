@@ -478,7 +478,7 @@ def test_global_vector_mode_equals_lds_mode(device, mode, xl, overrides):
 @pytest.mark.parametrize("shape", [(4, 1500, False), (2, 2048, True)])
 def test_lds_staged_history_is_bitwise_the_register_pass(device, shape, overrides):
     """The global-vector solve with the XL image streams its history rows HBM -> LDS by global_load_lds
-    one entry ahead (bfgs_solve.hip, wide_direction STAGED: rows of >= 3 float4 groups per thread, so
+    one entry ahead (solve_passes.hpp, wide_direction STAGED: rows of >= 3 float4 groups per thread, so
     P > 4096 -- here 4521 and 6158); without the XL image (DAVA_GV_NO_XL) the same pass loads them into
     registers.  The objective reads the same values from LDS or from the workspace, so the two solves --
     parameters and status words -- must be bitwise equal."""

@@ -1,13 +1,12 @@
 // Microbenchmark (not part of the library): the LDS-mode solve's own history pass,
-// dava::compact_products_fused<GM, NW> from csrc/bfgs_solve.hip, run back to back over a history that
+// dava::compact_products_fused<GM, NW> from csrc/solve_passes.hpp, run back to back over a history that
 // grows by one entry per "iteration" -- the memory pattern of tools/micro/history_stream.hip, but with
 // the solve's code (buffer loads, per-entry coefficient reads, priority drop, deferred cross-wave
 // combine) instead of a stand-in loop.  Next to it the stand-in loop's kernel is rebuilt here on the
 // same (non-zero) rows, so the two rates compare directly.  Prints GB/s of history rows read.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -I../../include
 //        -I../../deep-attention-visual-odometry_amd/csrc solve_pass_stream.hip -o solve_pass_stream
-#define DAVA_DEVICE_PASSES_ONLY 1  // the device passes only, not the solve kernels and host API
-#include "../../deep-attention-visual-odometry_amd/csrc/bfgs_solve.hip"
+#include "solve_passes.hpp"
 
 #include <cstdio>
 #include <cstdlib>

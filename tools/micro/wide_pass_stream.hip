@@ -1,5 +1,5 @@
 // Microbenchmark (not part of the library): the global-vector solve's history pass alone --
-// dava::wide_direction<GT, 8, STAGED> from csrc/bfgs_solve.hip (C5: P = 12,381, GT = 7 float4 groups per
+// dava::wide_direction<GT, 8, STAGED> from csrc/solve_passes.hpp (C5: P = 12,381, GT = 7 float4 groups per
 // thread, eight waves, one workgroup per problem) -- run back to back over a history that grows by one
 // entry per "iteration", as the solve does, with nothing else on the CU.  STAGED = the solve's XL form
 // (rows HBM -> LDS by global_load_lds one entry ahead; with 3 row slots 1.5 entries ahead, the LDS the
@@ -9,8 +9,7 @@
 // the solve at B = 256).
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -I../../include
 //        -I../../deep-attention-visual-odometry_amd/csrc wide_pass_stream.hip -o wide_pass_stream
-#define DAVA_DEVICE_PASSES_ONLY 1  // the device passes only, not the solve kernels and host API
-#include "../../deep-attention-visual-odometry_amd/csrc/bfgs_solve.hip"
+#include "solve_passes.hpp"
 
 #include <cstdio>
 #include <cstdlib>
