@@ -60,9 +60,16 @@ typedef float pf2 __attribute__((ext_vector_type(2)));
 // ---- Taylor-branched ratios, same thresholds and series as the reference ----
 // (templated on the scalar: float, or Dual for second derivatives, dava_dual.hpp)
 // sx, cx: sin x and cos x, computed once by the caller (sincos_)
+// Constants that a float does not hold exactly (the thresholds, -1/3, the z' nudge) are written in the
+// scalar's real type R: for float and Dual the float constants they always were, for double the
+// reference's double values.  The other series coefficients are small integers, exact in either.
+static_assert((float)0.01 == 0.01f && (float)0.05 == 0.05f && (float)1e-8 == 1e-8f &&
+                  (float)-1.0 / (float)3.0 == -1.0f / 3.0f,
+              "the fp32 instantiations keep their constants");
 template <typename S>
 __device__ __forceinline__ S sinc(S x, S sx) {
-  if (fabs_(x) < 0.01f) {
+  using R = real_t<S>;
+  if (fabs_(x) < S(R(0.01))) {
     const S x2 = x * x, x4 = x2 * x2, x6 = x4 * x2;
     return 1.0f - x2 / 6.0f + x4 / 120.0f - x6 / 5040.0f;
   }
@@ -70,17 +77,19 @@ __device__ __forceinline__ S sinc(S x, S sx) {
 }
 template <typename S>
 __device__ __forceinline__ S sinc_slope(S x, S sx, S cx) {  // cos/x^2 - sin/x^3
+  using R = real_t<S>;
   const S x2 = x * x;
-  if (fabs_(x) < 0.01f) {
+  if (fabs_(x) < S(R(0.01))) {
     const S x4 = x2 * x2, x6 = x4 * x2;
-    return -1.0f / 3.0f + x2 / 30.0f - x4 / 840.0f + x6 / 45360.0f;
+    return R(-1.0) / R(3.0) + x2 / 30.0f - x4 / 840.0f + x6 / 45360.0f;
   }
   return cx / x2 - sx / (x * x2);
 }
 template <typename S>
 __device__ __forceinline__ S versine_ratio(S x, S cx) {  // (1 - cos x)/x^2
+  using R = real_t<S>;
   const S x2 = x * x;
-  if (fabs_(x) < 0.05f) {
+  if (fabs_(x) < S(R(0.05))) {
     const S x4 = x2 * x2, x6 = x4 * x2;
     return 0.5f - x2 / 24.0f + x4 / 720.0f - x6 / 40320.0f;
   }
@@ -111,7 +120,7 @@ struct Intrinsics {
 };
 
 template <bool TRIAL, typename S>
-__device__ __forceinline__ S trial_value(const S* x, const S* d, float a, int i) {
+__device__ __forceinline__ S trial_value(const S* x, const S* d, real_t<S> a, int i) {
   if constexpr (TRIAL) return fadd_rn(x[i], fmul_rn(S(a), d[i]));
   else return x[i];
 }
@@ -128,7 +137,7 @@ struct RayAngle {
   S cx, cy, F, Fp;  // principal point, focal elu(f) + 1 and its derivative
   S dcx, dcy, dF;   // SLOPE: tangents
 };
-constexpr float kRayEps = 2.220446049250313e-16f;
+constexpr float kRayEps = 2.220446049250313e-16f;  // 2^-52: exact as a float and as a double
 
 // Every division by a norm is a multiplication by its reciprocal (one IEEE division per norm instead
 // of one per component: ~16 -> 7 division sequences per (view, point) pair; C3 ray 180k -> 204k
@@ -211,10 +220,12 @@ __device__ __forceinline__ void ray_angle_pair(const RayAngle<S>& ra, const S (&
 template <bool GRAD, bool SLOPE, bool TRIAL, bool DOT = false, bool CHECK = false,
           int RES = DAVA_RESIDUAL_SQUARED_REPROJECTION, typename S = float, int NW = kWaves, int PPT = 0,
           bool PACK = false>
-__device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d, float alpha, const float* obs,
-                                        const uint8_t* vis, S* grad, S* views, S* vpart, float* scratch, int& buf,
-                                        S& E_out, S& slope_out, S* obs_grad = nullptr,
-                                        float* obs_tangent_acc = nullptr, const float* obs_dir = nullptr) {
+__device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d, real_t<S> alpha,
+                                        const real_t<S>* obs, const uint8_t* vis, S* grad, S* views, S* vpart,
+                                        real_t<S>* scratch, int& buf, S& E_out, S& slope_out, S* obs_grad = nullptr,
+                                        real_t<S>* obs_tangent_acc = nullptr, const real_t<S>* obs_dir = nullptr) {
+  using Real = real_t<S>;  // float (S = float, Dual) or double
+  static_assert(!std::is_same<S, double>::value || (PPT == 0 && !PACK), "the double objective: PPT = 0, no PACK");
   constexpr int BLOCK = kWave * NW;  // threads in the workgroup
   static_assert(!DOT || (GRAD && !SLOPE), "DOT derives the slope from the reverse-mode gradient");
   static_assert(!CHECK || TRIAL, "CHECK needs a trial point");
@@ -311,7 +322,7 @@ __device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d,
   const S s = (ps * fN + cs * fM) / fNM;
   const S inv_s = 1.0f / s;
   // the distorted model's z' == 0 -> 1e-8 (distorted_camera_model.py:57); -0 for the pinhole model
-  const float z_nudge = L.distort ? 1e-8f : -0.0f;
+  const Real z_nudge = L.distort ? Real(1e-8) : Real(-0.0);
   S ds_over_s = 0.f;
   if constexpr (SLOPE) {
     const S ds = ((sums[1] / (3.0f * fN)) * fN + (tdsum / (3.0f * (float)(M - 1))) * fM) / fNM;
@@ -415,7 +426,7 @@ __device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d,
       // the pair's observation; for dual numbers with an observation direction (second derivatives in the
       // observations, ba_second_order) it carries that tangent
       S ob[2] = {obs[2 * (m * N + n)], obs[2 * (m * N + n) + 1]};
-      if constexpr (!std::is_same<S, float>::value) {
+      if constexpr (std::is_same<S, Dual>::value) {
         if (obs_dir) {
           ob[0] = S(obs[2 * (m * N + n)], obs_dir[2 * (m * N + n)]);
           ob[1] = S(obs[2 * (m * N + n) + 1], obs_dir[2 * (m * N + n) + 1]);
@@ -471,7 +482,7 @@ __device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d,
         // projection; the distorted model nudges z' == 0 by 1e-8 (distorted_camera_model.py:57)
         // branch-free: + (-0) leaves every p2 (signed zeros included) bit for bit, so the pinhole
         // model is untouched; a runtime-uniform branch here cost C2 5% (profiles/r03_ab_c2_regression_bisect.log)
-        p2 = p2 + (p2 == S(0.0f) ? z_nudge : -0.0f);
+        p2 = p2 + (p2 == S(0.0f) ? z_nudge : Real(-0.0));
         const S iz = 1.0f / p2;
         const S qx = p0 * iz, qy = p1 * iz;
         const S ub = in.f * qx, vb = in.f * qy;
@@ -537,7 +548,7 @@ __device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d,
         ray_angle_pair<GRAD, SLOPE, S>(ra, ob, visible, p0, p1, p2, dp0, dp1, dp2, e_loc, sl_loc, gin, G0, G1, G2,
                                        go0, go1);
       }
-      if constexpr (GRAD && !std::is_same<S, float>::value) {
+      if constexpr (GRAD && std::is_same<S, Dual>::value) {
         const int pr = m * N + n;
         if (obs_grad) {
           obs_grad[2 * pr] = go0;

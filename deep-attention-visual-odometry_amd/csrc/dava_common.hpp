@@ -56,6 +56,9 @@ __device__ __forceinline__ T clamp_min(T v, T lo) { return v < lo ? lo : v; }
 
 // sign() as torch.abs backward uses it: 0 at 0.
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+__device__ __forceinline__ double sgn(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
+// (a double clamped at a bound held as a float constant, kRayEps: the bound widens exactly)
+__device__ __forceinline__ double clamp_min(double v, float lo) { return v < lo ? (double)lo : v; }
 
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
@@ -169,6 +172,30 @@ __device__ __forceinline__ void block_sum(float (&v)[R], float* scratch, int buf
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     float t = s[r];  // wave partials added in wave order
+#pragma unroll
+    for (int w = 1; w < NW; ++w) t += s[w * 32 + r];
+    v[r] = t;
+  }
+}
+
+// The same for doubles (the float64 objective and solve, bfgs_solve_f64.hip): xor butterflies (every lane adds
+// the same pair at every step, so all lanes hold one value), then the NW wave partials in wave order.
+// `scratch` holds 2 x NW x 32 doubles, double-buffered by the caller as above.
+template <int R, int NW = kWaves>
+__device__ __forceinline__ void block_sum(double (&v)[R], double* scratch, int buf) {
+  static_assert(R <= 32, "scratch rows hold 32 values");
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  double* s = scratch + buf * (NW * 32);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const double w = wave_sum(v[r]);
+    if (lane == 0) s[wave * 32 + r] = w;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    double t = s[r];  // wave partials added in wave order
 #pragma unroll
     for (int w = 1; w < NW; ++w) t += s[w * 32 + r];
     v[r] = t;

@@ -51,7 +51,20 @@ __device__ __forceinline__ bool operator<=(Dual a, Dual b) { return a.v <= b.v; 
 __device__ __forceinline__ bool operator>=(Dual a, Dual b) { return a.v >= b.v; }
 __device__ __forceinline__ bool operator==(Dual a, Dual b) { return a.v == b.v; }
 
-// ---- elementary functions, float and Dual ----
+// The real type a scalar is built on: float for float and Dual, double for double.  Step sizes, observations,
+// reduction scratch and constants of the objective code have this type.
+template <typename S>
+struct RealOf {
+  using type = float;
+};
+template <>
+struct RealOf<double> {
+  using type = double;
+};
+template <typename S>
+using real_t = typename RealOf<S>::type;
+
+// ---- elementary functions: float, Dual and (below) double ----
 __device__ __forceinline__ float sqrt_(float x) { return sqrtf(x); }
 __device__ __forceinline__ float sin_(float x) { return sinf(x); }
 __device__ __forceinline__ float cos_(float x) { return cosf(x); }
@@ -93,6 +106,19 @@ __device__ __forceinline__ float value_of(Dual x) { return x.v; }
 // sign(x) as torch.abs backward uses it: piecewise constant, zero derivative
 __device__ __forceinline__ Dual sgn(Dual x) { return Dual(sgn(x.v)); }
 __device__ __forceinline__ Dual clamp_min(Dual v, float lo) { return v.v < lo ? Dual(lo) : v; }
+
+// double (the float64 objective): the correctly rounded add / multiply for trial points, as for float
+__device__ __forceinline__ double sqrt_(double x) { return sqrt(x); }
+__device__ __forceinline__ double sin_(double x) { return sin(x); }
+__device__ __forceinline__ double cos_(double x) { return cos(x); }
+__device__ __forceinline__ double fabs_(double x) { return fabs(x); }
+__device__ __forceinline__ double exp_(double x) { return exp(x); }
+__device__ __forceinline__ double expm1_(double x) { return expm1(x); }
+__device__ __forceinline__ double atan2_(double y, double x) { return atan2(y, x); }
+__device__ __forceinline__ double fmul_rn(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double fadd_rn(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ double value_of(double x) { return x; }
+__device__ __forceinline__ void sincos_(double x, double& s, double& c) { sincos(x, &s, &c); }
 
 template <>
 __device__ __forceinline__ Dual wave_sum<Dual>(Dual x) {

@@ -78,6 +78,23 @@ class DavaSolverConfig(ctypes.Structure):
     ]
 
 
+class DavaSceneF64(ctypes.Structure):
+    """DavaScene with float64 observations (the `_f64` entry points)."""
+    _fields_ = list(DavaScene._fields_)
+
+
+class DavaSolverConfigF64(ctypes.Structure):
+    _fields_ = [
+        ("sufficient_decrease", ctypes.c_double),
+        ("curvature", ctypes.c_double),
+        ("error_threshold", ctypes.c_double),
+        ("minimum_step", ctypes.c_double),
+        ("iterations", _c_i32),
+        ("max_line_search_trials", _c_i32),
+        ("strong_wolfe", _c_i32),
+    ]
+
+
 class DavaSolvePlan(ctypes.Structure):
     _fields_ = [
         ("global_vectors", _c_i32),
@@ -95,6 +112,11 @@ SIGNATURES = {
     "dava_ba_solve": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSolverConfig), _vp, _vp, _vp, _vp,
                                      _vp, ctypes.c_size_t, _vp]),
     "dava_ba_evaluate": (ctypes.c_int, [ctypes.POINTER(DavaScene), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dava_ba_solve_workspace_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                            ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSolverConfigF64), _vp, _vp,
+                                         _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dava_ba_evaluate_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dava_ba_second_order": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 8),
     "dava_ba_second_order_obs": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 9),
     "dava_ba_solve_tape_bytes": (ctypes.c_size_t, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSolverConfig)]),

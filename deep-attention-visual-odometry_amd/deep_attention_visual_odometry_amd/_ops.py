@@ -46,6 +46,21 @@ def scene_struct(observations: Optional[Tensor], visibility: Optional[Tensor], n
                        N.ptr(observations), N.ptr(visibility), residual)
 
 
+def scene_struct_f64(observations: Optional[Tensor], visibility: Optional[Tensor], num_views: int, num_points: int,
+                     distortion: bool, batch: int,
+                     residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> N.DavaSceneF64:
+    return N.DavaSceneF64(batch, num_views, num_points, 1 if distortion else 0,
+                          num_parameters(num_views, num_points, distortion),
+                          N.ptr(observations), N.ptr(visibility), residual)
+
+
+def solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
+                      max_line_search_trials, strong) -> N.DavaSolverConfigF64:
+    return N.DavaSolverConfigF64(float(sufficient_decrease), float(curvature), float(error_threshold),
+                                 float(minimum_step), int(iterations), int(max_line_search_trials),
+                                 1 if strong else 0)
+
+
 def solver_config(sufficient_decrease, curvature, error_threshold, iterations, minimum_step, max_line_search_trials,
                   strong, hessian_mode, drop_path_p: float = 0.0, drop_seed: int = 0,
                   return_second_last: bool = False) -> N.DavaSolverConfig:
@@ -67,11 +82,19 @@ def _check_scene_tensors(x: Tensor, observations: Tensor, visibility: Tensor, nu
         raise ValueError(f"observations must be ({b}, {num_views}, {num_points}, 2), got {tuple(observations.shape)}")
     if tuple(visibility.shape) != (b, num_views, num_points):
         raise ValueError(f"visibility must be ({b}, {num_views}, {num_points}), got {tuple(visibility.shape)}")
-    if observations.dtype != torch.float32 or visibility.dtype != torch.uint8:
-        raise TypeError("observations must be float32 and visibility uint8")
+    if x.dtype not in (torch.float32, torch.float64) or observations.dtype != x.dtype \
+            or visibility.dtype != torch.uint8:
+        raise TypeError("parameters and observations must both be float32 or both float64 (observations "
+                        f"{observations.dtype}, parameters {x.dtype}) and visibility uint8")
     for t in (x, observations, visibility):
         if not t.is_contiguous() or t.device != x.device:
             raise ValueError("scene tensors must be contiguous and on one device")
+
+
+def _require_float32(x: Tensor, what: str) -> None:
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what} are float32 only (got {x.dtype}); the float64 flavour covers ba_solve and "
+                        "ba_evaluate")
 
 
 # ---------------------------------------------------------------- fused BA ops
@@ -85,11 +108,36 @@ def ba_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: in
     """``dava_ba_solve``: the whole eval-mode BFGS solve of a (B, P) fp32 batch in one launch.
     ``workspace``: a uint8 scratch buffer of at least ``dava_ba_solve_workspace_bytes`` (its contents
     are overwritten), or an empty tensor to allocate one per call.
-    Returns (x, error (B,) or empty, status (B, 4) int32)."""
+    Returns (x, error (B,) or empty, status (B, 4) int32).
+    A float64 batch (parameters and observations) runs ``dava_ba_solve_f64``: compact history, eval mode."""
     lib = N.load_library()
     _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
     b = x0.shape[0]
     dev = x0.device
+    if x0.dtype == torch.float64:
+        if hessian_mode != N.DAVA_HESSIAN_COMPACT or drop_path_p != 0.0 or return_second_last:
+            raise ValueError("the float64 fused solve runs the compact history in eval mode only "
+                             "(hessian_mode == DAVA_HESSIAN_COMPACT, drop_path_p == 0, no return_second_last)")
+        sc64 = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+        cfg64 = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
+                                  max_line_search_trials, strong)
+        need = int(lib.dava_ba_solve_workspace_bytes_f64(sc64, cfg64))
+        if need == 0:
+            raise ValueError("this scene / configuration has no float64 fused solve (the LDS image must fit "
+                             "160 KiB, 1 <= iterations <= 1025)")
+        if workspace.numel() < need or workspace.device != dev or workspace.dtype != torch.uint8:
+            if workspace.numel() > 0:
+                raise ValueError(f"workspace holds {workspace.numel()} bytes, the solve needs {need} "
+                                 "(uint8, same device)")
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        x_out = torch.empty_like(x0)
+        err = torch.empty(b, device=dev, dtype=torch.float64) if want_error else _empty0(x0)
+        status = torch.empty((b, N.STATUS_WORDS), device=dev, dtype=torch.int32)
+        with torch.cuda.device(dev):
+            N.check(lib.dava_ba_solve_f64(sc64, cfg64, N.ptr(x0), N.ptr(x_out), N.ptr(err) if want_error else None,
+                                          N.ptr(status), N.ptr(workspace), workspace.numel(), N.stream_of(dev)),
+                    "dava_ba_solve_f64")
+        return x_out, err, status
     sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
     cfg = solver_config(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
                         max_line_search_trials, strong, hessian_mode, drop_path_p, drop_seed, return_second_last)
@@ -147,17 +195,25 @@ def ba_evaluate(x: Tensor, observations: Tensor, visibility: Tensor, num_views: 
     _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
     b = x.shape[0]
     for t in (direction, alpha):
-        if t is not None and (t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError("direction / alpha must be contiguous float32 on the parameters' device")
+        if t is not None and (t.device != x.device or t.dtype != x.dtype or not t.is_contiguous()):
+            raise ValueError("direction / alpha must be contiguous, of the parameters' dtype and on their device")
     if direction is not None and direction.shape != x.shape:
         raise ValueError("direction must have the parameters' shape")
     if alpha is not None and alpha.numel() != b:
         raise ValueError("alpha must hold one value per problem")
     if want_slope and direction is None:
         raise ValueError("the slope needs a direction")
-    err = torch.empty(b, device=x.device, dtype=torch.float32)
+    err = torch.empty(b, device=x.device, dtype=x.dtype)
     grad = torch.empty_like(x) if want_grad else _empty0(x)
-    slope = torch.empty(b, device=x.device, dtype=torch.float32) if want_slope else _empty0(x)
+    slope = torch.empty(b, device=x.device, dtype=x.dtype) if want_slope else _empty0(x)
+    if x.dtype == torch.float64:
+        sc64 = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+        with torch.cuda.device(x.device):
+            N.check(lib.dava_ba_evaluate_f64(sc64, N.ptr(x), N.ptr(direction), N.ptr(alpha), N.ptr(err),
+                                             N.ptr(grad) if want_grad else None,
+                                             N.ptr(slope) if want_slope else None, N.stream_of(x.device)),
+                    "dava_ba_evaluate_f64")
+        return err, grad, slope
     sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
     with torch.cuda.device(x.device):
         N.check(lib.dava_ba_evaluate(sc, N.ptr(x), N.ptr(direction), N.ptr(alpha), N.ptr(err),
@@ -181,6 +237,7 @@ def ba_second_order(x: Tensor, observations: Tensor, visibility: Tensor, num_vie
     """``dava_ba_second_order_obs``: (E, dE/dx, H v + (d2E/dx dobs) u, dE/dobs, (d2E/dobs dx) v + (d2E/dobs2) u),
     forward-over-reverse.  direction / obs_direction None mean v = 0 / u = 0.  Unrequested outputs are empty."""
     lib = N.load_library()
+    _require_float32(x, "second derivatives of the fused objectives")
     _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
     if direction is not None and (direction.shape != x.shape or direction.dtype != torch.float32
                                   or not direction.is_contiguous()):
@@ -222,6 +279,7 @@ def ba_solve_record(x0: Tensor, observations: Tensor, visibility: Tensor, num_vi
     """``dava_ba_solve_record``: the fused COMPACT solve (bitwise ``ba_solve``'s x and status) plus the
     tape the adjoint replays.  Returns (x, status (B, 4) int32, tape uint8)."""
     lib = N.load_library()
+    _require_float32(x0, "the recording solve")
     _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
     b, dev = x0.shape[0], x0.device
     sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
@@ -259,6 +317,7 @@ def ba_solve_backward(x_out_grad: Tensor, tape: Tensor, status: Tensor, observat
                       want_observations: bool) -> Tuple[Tensor, Tensor]:
     """``dava_ba_solve_backward``: (dL/dx0, dL/dobs or empty) of a recorded solve for dL/dx_out."""
     lib = N.load_library()
+    _require_float32(x_out_grad, "the fused solve's adjoint")
     _check_scene_tensors(x_out_grad, observations, visibility, num_views, num_points, distortion)
     b, dev = x_out_grad.shape[0], x_out_grad.device
     if tuple(status.shape) != (b, N.STATUS_WORDS) or status.dtype != torch.int32 or not status.is_contiguous():

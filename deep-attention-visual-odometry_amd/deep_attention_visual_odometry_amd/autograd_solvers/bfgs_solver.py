@@ -24,6 +24,11 @@ line search is detached, as in the reference.  A fused objective
 double backward is the forward-over-reverse kernel (H v and the observation
 cross term, csrc/ba_second_order.hip), so gradients reach captured observations.
 
+float64: an objective built from float64 device observations also solves float64 parameters in one launch
+(``dava_ba_solve_f64``: compact history, eval-mode semantics, no graph); what that kernel does not cover
+(dense mode, more than 1025 iterations, training mode's drop path) runs the generic loop with the float64
+objective as its closure, and float64 parameters that require grad raise ``TypeError``.
+
 Training mode's ``return_second_last`` runs fused too (a problem stopped by the minimum-step rule
 keeps x before its last step); when the reference's scatter would have moved rows between problems
 (``native_ops.second_last_moves_rows``) the solve is redone by the generic loop, which reproduces it.
@@ -121,6 +126,9 @@ class BFGSSolver(Module):
         drop_p = self.drop_path_p if self.training else 0.0
         second_last = self.training and self.return_second_last
         generic_training = drop_p > 0.0 and _native.python_knob("GENERIC_TRAINING")  # torch-RNG generic loop
+        if (isinstance(error_function, ReprojectionError) and parameters.dtype == torch.float64
+                and error_function.observations64 is not None):
+            return self._forward_f64(parameters, error_function, error_threshold, num_iterations, drop_p, second_last)
         if isinstance(error_function, ReprojectionError) and not generic_training:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0.0 else 0  # from torch's default generator
             out = None
@@ -220,6 +228,35 @@ class BFGSSolver(Module):
             error_threshold=error_threshold, iterations=num_iterations, minimum_step=self.minimum_step,
             hessian_mode=mode, want_status=True, residual=fn.residual, drop_path_p=drop_p, drop_seed=seed,
             return_second_last=second_last)
+        self.last_status = status
+        return x.reshape(parameters.shape)
+
+    def _forward_f64(self, parameters, fn: ReprojectionError, error_threshold, num_iterations, drop_p, second_last):
+        """float64 parameters on an objective built from float64 device observations: one launch of
+        ``dava_ba_solve_f64`` (compact history, eval-mode semantics) where it applies, else the generic loop
+        with the objective as its closure (its float64 value and first derivative are HIP kernels too).
+        Differentiating through a float64 solve is not available: second derivatives are float32 only."""
+        if parameters.requires_grad:
+            raise TypeError("differentiating through a float64 solve needs second derivatives of the fused "
+                            "objectives, which are float32 only")
+        lead = parameters.shape[:-1]
+        if fn.batch_shape != lead:
+            raise ValueError(f"ReprojectionError batch shape {tuple(fn.batch_shape)} != parameters {tuple(lead)}")
+        x0 = parameters.reshape(-1, parameters.size(-1))
+        fused = (drop_p == 0.0 and not second_last and self.hessian_mode != "dense"
+                 and 1 <= num_iterations <= self.MAX_COMPACT_ENTRIES + 1
+                 and native_ops.solve_workspace_bytes_f64(max(x0.shape[0], 1), fn.num_views, fn.num_points,
+                                                          fn.distortion, num_iterations, fn.residual) > 0)
+        if not fused:
+            self.last_status = None  # the generic loop has no status words
+            self._check_generic_fits(parameters, num_iterations, second_last)
+            return self._generic(parameters, fn, error_threshold, num_iterations)
+        x, _, status = native_ops.ba_solve(
+            x0, fn.observations64.reshape(-1, fn.num_views, fn.num_points, 2),
+            fn.visibility.reshape(-1, fn.num_views, fn.num_points), fn.num_views, fn.num_points, fn.distortion,
+            sufficient_decrease=self.sufficient_decrease, curvature=self.curvature, error_threshold=error_threshold,
+            iterations=num_iterations, minimum_step=self.minimum_step, hessian_mode=_native.DAVA_HESSIAN_COMPACT,
+            want_status=True, residual=fn.residual)
         self.last_status = status
         return x.reshape(parameters.shape)
 

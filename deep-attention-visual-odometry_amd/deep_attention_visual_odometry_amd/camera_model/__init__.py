@@ -47,6 +47,10 @@ def unpack_calibration_parameters(parameters: torch.Tensor, num_views: int, num_
     )
 
 
+_F64_FIRST_ORDER_ONLY = ("the float64 fused objectives give E and dE/dx only: second derivatives and the "
+                         "observation gradient are float32 only")
+
+
 class _NativeObjective(torch.autograd.Function):
     """E(x, obs) per row from the HIP objective kernel.  Its backward is itself
     differentiable (``_NativeGradient``), so ``torch.autograd.grad(..., create_graph=True)``
@@ -56,6 +60,8 @@ class _NativeObjective(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, observations, visibility, num_views, num_points, distortion, residual):
         need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if need_obs and x.dtype == torch.float64:
+            raise TypeError(_F64_FIRST_ORDER_ONLY + " (the observations require grad)")
         if need_obs:  # dE/dobs comes from the second-order kernel (v = 0)
             err, grad, _, obs_grad, _ = native_ops.ba_second_order(
                 x, observations, visibility, num_views, num_points, distortion, residual=residual, want_hv=False)
@@ -72,6 +78,8 @@ class _NativeObjective(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, obs, vis = ctx.saved_tensors
         need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if torch.is_grad_enabled() and x.dtype == torch.float64:
+            raise TypeError(_F64_FIRST_ORDER_ONLY + " (create_graph)")
         if torch.is_grad_enabled():  # create_graph: keep the gradient differentiable
             grad, obs_grad = _NativeGradient.apply(x, obs, vis, *ctx.meta)
         else:
@@ -115,7 +123,8 @@ class ReprojectionError:
     E(x) = sum_{m,n} vis[m,n] || pi_m(X_n) - obs[m,n] ||^2
 
     observations: (B..., M, N, 2) float32, visibility: (B..., M, N) bool/0-1,
-    on the same ROCm device as the parameters.  With ``distortion=True`` the
+    on the same ROCm device as the parameters.  float64 device observations also enable the float64
+    kernels: float64 parameters then evaluate and solve in float64 (value and first derivative only).  With ``distortion=True`` the
     five Brown-Conrady coefficients (k1 k2 k3 p1 p2) are appended to the
     parameter vector (``camera_model/distorted_camera_model.py:59-86``).
     """
@@ -130,6 +139,11 @@ class ReprojectionError:
             raise ValueError("num_views must be >= 2")
         # (device tensors: the kernels read float32; CPU tensors keep their dtype for the torch objective)
         self.observations = observations if observations.device.type == "cpu" else observations.to(torch.float32)
+        # float64 device observations are the opt-in to the float64 kernels: kept beside the float32 copy, and
+        # float64 parameters then evaluate (and solve) in float64.  Built from float32 observations the
+        # objective stays float32 only, as before.
+        self.observations64 = (observations if observations.device.type != "cpu"
+                               and observations.dtype == torch.float64 else None)
         self.visibility = visibility.to(torch.uint8)
         self.num_views = int(num_views)
         self.num_points = int(num_points)
@@ -148,7 +162,12 @@ class ReprojectionError:
     def __call__(self, parameters: torch.Tensor, batch_mask: torch.Tensor) -> torch.Tensor:
         if parameters.size(-1) != self.num_parameters:
             raise ValueError(f"expected {self.num_parameters} parameters, got {parameters.size(-1)}")
-        obs = self.observations[batch_mask]
+        on_device = parameters.device.type != "cpu"
+        if on_device and parameters.dtype == torch.float64 and self.observations64 is None:
+            raise TypeError("ReprojectionError evaluates in float32 (construct it from float64 observations to "
+                            "evaluate float64 parameters)")
+        use64 = on_device and parameters.dtype == torch.float64
+        obs = (self.observations64 if use64 else self.observations)[batch_mask]
         vis = self.visibility[batch_mask]
         lead = parameters.shape[:-1]
         x = parameters.reshape(-1, parameters.size(-1))
@@ -159,8 +178,8 @@ class ReprojectionError:
             # the parameters live, as the reference does (bfgs_solver.py:94-117); autograd gives its derivatives
             # to any order.  Device tensors take the HIP kernels below, never this.
             return self._torch_objective(x, obs.to(x.dtype), vis).reshape(lead)
-        if x.dtype != torch.float32:
-            raise TypeError("ReprojectionError evaluates in float32")
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError("ReprojectionError evaluates in float32 (or float64, built from float64 observations)")
         err = _NativeObjective.apply(x, obs, vis, self.num_views, self.num_points, self.distortion, self.residual)
         return err.reshape(lead)
 

@@ -21,7 +21,10 @@ def _c(t: torch.Tensor) -> torch.Tensor:
 
 def _scene_inputs(x: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor):
     dev = x.device
-    obs = _c(observations.detach().to(device=dev, dtype=torch.float32))
+    if x.dtype == torch.float64 and observations.dtype != torch.float64:
+        # float64 is opt-in through the observations: nothing is widened silently
+        raise TypeError(f"float64 parameters need float64 observations (got {observations.dtype})")
+    obs = _c(observations.detach().to(device=dev, dtype=x.dtype))
     vis = _c(visibility.detach().to(device=dev, dtype=torch.uint8))
     return obs, vis
 
@@ -33,8 +36,16 @@ def _fp32_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
     return _c(x.detach())
 
 
-def _opt(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    return None if t is None else _c(t.detach().to(torch.float32))
+def _float_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
+    """float32, or float64 for the entry points that have the float64 flavour (ba_evaluate, ba_solve)."""
+    N.require_device_tensor(x, what)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"the fused BA kernels compute in float32 or float64, got {x.dtype}")
+    return _c(x.detach())
+
+
+def _opt(t: Optional[torch.Tensor], dtype: torch.dtype = torch.float32) -> Optional[torch.Tensor]:
+    return None if t is None else _c(t.detach().to(dtype))
 
 
 def ba_evaluate(x: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
@@ -42,11 +53,13 @@ def ba_evaluate(x: torch.Tensor, observations: torch.Tensor, visibility: torch.T
                 alpha: Optional[torch.Tensor] = None, want_grad: bool = True, want_slope: bool = False,
                 residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION,
                 ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """E, dE/dx, d.dE/dx at x + alpha*direction for a (B, P) fp32 batch (``torch.ops.dava.ba_evaluate``)."""
-    x = _fp32_on_device(x, "x")
+    """E, dE/dx, d.dE/dx at x + alpha*direction for a (B, P) batch (``torch.ops.dava.ba_evaluate``): float32, or
+    float64 parameters with float64 observations (direction and alpha are taken in the parameters' dtype)."""
+    x = _float_on_device(x, "x")
     obs, vis = _scene_inputs(x, observations, visibility)
     err, grad, slope = torch.ops.dava.ba_evaluate(x, obs, vis, num_views, num_points, bool(distortion),
-                                                  _opt(direction), _opt(alpha), bool(want_grad), bool(want_slope),
+                                                  _opt(direction, x.dtype), _opt(alpha, x.dtype), bool(want_grad),
+                                                  bool(want_slope),
                                                   int(residual))
     return err, (grad if want_grad else None), (slope if want_slope else None)
 
@@ -79,8 +92,10 @@ def ba_solve(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Ten
     """One fused launch for the whole batch (``torch.ops.dava.ba_solve``).  Returns (x, error|None, status|None).
     ``drop_path_p`` > 0: training mode's drop path with the counter-based schedule of ``drop_seed``.
     ``return_second_last``: a problem stopped by the minimum-step rule returns x before its last step
-    (see :func:`second_last_moves_rows` for the one case the reference does differently)."""
-    x0 = _fp32_on_device(x0, "parameters")
+    (see :func:`second_last_moves_rows` for the one case the reference does differently).
+    float64 parameters with float64 observations run the float64 solve: ``hessian_mode`` must be
+    ``DAVA_HESSIAN_COMPACT``, ``drop_path_p`` 0 and ``return_second_last`` off."""
+    x0 = _float_on_device(x0, "parameters")
     obs, vis = _scene_inputs(x0, observations, visibility)
     x, err, status = torch.ops.dava.ba_solve(
         x0, obs, vis, int(num_views), int(num_points), bool(distortion), float(sufficient_decrease),
@@ -183,6 +198,16 @@ def solve_workspace_bytes(batch: int, num_views: int, num_points: int, distortio
     sc = scene_struct(None, None, num_views, num_points, distortion, batch)
     cfg = solver_config(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True, hessian_mode)
     return int(lib.dava_ba_solve_workspace_bytes(sc, cfg))
+
+
+def solve_workspace_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1000,
+                              residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_solve_workspace_bytes_f64`` (host-only): 0 where the float64 fused solve does not run."""
+    from ._ops import scene_struct_f64, solver_config_f64
+
+    sc = scene_struct_f64(None, None, num_views, num_points, distortion, batch, residual)
+    cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
+    return int(N.load_library().dava_ba_solve_workspace_bytes_f64(sc, cfg))
 
 
 def solve_plan(batch: int, num_views: int, num_points: int, distortion: bool,

@@ -21,9 +21,12 @@
  *    inputs are never written; outputs may not alias inputs unless stated.
  *  - Return value: DAVA_OK or a DAVA_ERR_* code; nothing throws across the ABI.
  *    dava_status_string() turns a code into text.
- *  - fp32 throughout the fused solver (the reference's dtype for the BA path);
- *    the generic BFGS building blocks come in _f32 and _f64 flavours because
- *    the reference's own unit tests drive them in float64.
+ *  - fp32 throughout the fused solver (the reference's dtype for the BA path),
+ *    with an opt-in float64 flavour of the objective evaluation and of the
+ *    one-launch COMPACT solve (the `_f64` entry points on DavaSceneF64: the
+ *    reference's training entry point and its solver / geometry tests run in
+ *    float64); the generic BFGS building blocks come in _f32 and _f64 flavours
+ *    because the reference's own unit tests drive them in float64.
  */
 #ifndef DAVA_BA_H
 #define DAVA_BA_H
@@ -192,6 +195,49 @@ int dava_ba_solve_backward(const DavaScene* scene, const DavaSolverConfig* confi
  *   slope_out (B)    d . dE/dx at the point (forward mode), or NULL (needs direction) */
 int dava_ba_evaluate(const DavaScene* scene, const float* x, const float* direction, const float* alpha,
                      float* error_out, float* grad_out, float* slope_out, void* stream);
+
+/* ---- float64 flavour of the evaluation and of the fused solve (additive to ABI 4) ----
+ * The same objectives and the same algorithm with every value a double: parameters, observations,
+ * thresholds (1e-4 as a double is the reference's 1e-4), history rows.  COMPACT inverse Hessian only,
+ * eval mode only (no drop path, no return_second_last, no tape), one 256-thread workgroup per problem
+ * with its whole state in LDS: a shape is supported when that image fits 160 KiB (C1-C3 do; C5 does
+ * not) and 1 <= iterations <= 1025.  Anything else: DAVA_ERR_UNSUPPORTED, and 0 from the size query. */
+typedef struct DavaSceneF64 {
+  int32_t batch;               /* B >= 0                               */
+  int32_t num_views;           /* M >= 2                               */
+  int32_t num_points;          /* N >= 1                               */
+  int32_t distortion;          /* 0 = pinhole, 1 = + Brown-Conrady     */
+  int32_t num_parameters;      /* P                                    */
+  const double* observations;  /* (B, M, N, 2) fp64                    */
+  const uint8_t* visibility;   /* (B, M, N) 0/1                        */
+  int32_t residual;            /* DavaResidual                         */
+} DavaSceneF64;
+
+typedef struct DavaSolverConfigF64 {
+  double sufficient_decrease;     /* c1, default 1e-4                          */
+  double curvature;               /* c2, default 0.9                           */
+  double error_threshold;         /* default 1e-4                              */
+  double minimum_step;            /* default 1e-8                              */
+  int32_t iterations;             /* 1 .. 1025                                 */
+  int32_t max_line_search_trials; /* 1000 in wolfe_conditions.py:116           */
+  int32_t strong_wolfe;           /* 1 (bfgs_solver.py:189)                    */
+} DavaSolverConfigF64;
+
+/* Bytes of device workspace dava_ba_solve_f64 needs: the history rows,
+ * B * 2 * max(iterations - 1, 1) * round_up(P, 4) * 8, followed by a 256-byte tail kept for a
+ * work-queue counter (this version launches one workgroup per problem and leaves it unused).
+ * 0 if the scene / config is invalid or unsupported.  dava_ba_solve_f64 requires a workspace of at
+ * least this size (tail included) whenever iterations > 1, else DAVA_ERR_WORKSPACE. */
+size_t dava_ba_solve_workspace_bytes_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config);
+
+/* dava_ba_solve in float64: x0, x_out (B, P) fp64 (may alias), error_out (B) fp64 or NULL,
+ * status_out (B, 4) int32 or NULL (the same four words). */
+int dava_ba_solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0, double* x_out,
+                      double* error_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dava_ba_evaluate in float64 (same NULL conventions). */
+int dava_ba_evaluate_f64(const DavaSceneF64* scene, const double* x, const double* direction, const double* alpha,
+                         double* error_out, double* grad_out, double* slope_out, void* stream);
 
 /* Second derivatives of the objective, for differentiating THROUGH a solve whose error
  * function is a fused objective (the reference's create_graph double backward,

@@ -1,0 +1,160 @@
+#!/usr/bin/env python
+"""GPU.  The float64 fused solve (dava_ba_solve_f64) measured against the fp32 fused solve and against the
+generic float64 loop, one JSON line per configuration (default: profiles/f64_solve.jsonl).
+
+  c2, c3         C2 (2 x 128, B = 1024) and C3 (4 x 256, Brown-Conrady, B = 8192) at K = 100 fixed
+                 iterations: float64 fused and float32 fused alternated in one process.
+  c3_b256_k20    C3 at B = 256, K = 20: float64 fused against the only float64 route there was before it, the
+                 drop-in's generic loop around the torch closure (geometry.closure_ops) in float64.
+
+Timing: device events around each solve, every shape warmed up first, median of --repeats (>= 5) solves.
+Reported: problems/s, algorithmic HBM bytes (bench.py's compact model; 8-byte elements for float64, computed
+here), the fraction of 8 TB/s they amount to, and the ratio to the fp32 fused rate.  The one requirement
+(exit status 1 otherwise): the fused float64 solve is faster than the generic float64 loop at the same shape.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "deep-attention-visual-odometry_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+PEAK_BYTES_PER_S = 8e12  # MI355X HBM3E
+
+
+def compact_algorithmic_bytes(p, mn, iters, element, lds_entries=0):
+    """bench.py's compact_algorithmic_bytes with `element`-byte values: iteration k >= 2 reads the k - 1 rows of
+    S and W once, iterations 1 .. K-1 append one row of each; observations (2 values) and visibility (1 byte)
+    per pair and x0 read once, x written once.  The oldest `lds_entries` entries never leave the CU."""
+    pv = (p + 3) // 4 * 4
+    reads = 2.0 * element * pv * sum(max(k - 1 - lds_entries, 0) for k in range(2, iters))
+    writes = 2.0 * element * pv * max(iters - 1 - lds_entries, 0)
+    return reads + writes + (2.0 * element + 1.0) * mn + 2.0 * element * p
+
+
+def timed(fn, repeats):
+    fn()  # warm-up of this shape (module load, allocator)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        fn()
+        end.record()
+        end.synchronize()
+        times.append(start.elapsed_time(end) * 1e-3)
+    return times
+
+
+def scene(b, m, n, distortion, dev):
+    from deep_attention_visual_odometry_amd import make_scenes
+
+    s = make_scenes(b, m, n, distortion=distortion, seed=7, drop=0.0 if distortion else 0.1)
+    return (torch.tensor(s.initial, device=dev), torch.tensor(s.observations, device=dev),
+            torch.tensor(s.visibility, device=dev).to(torch.uint8))
+
+
+def fused_pair(tag, b, m, n, distortion, k, repeats, dev):
+    """float64 fused and float32 fused, alternated solve by solve."""
+    from deep_attention_visual_odometry_amd import _native as N
+    from deep_attention_visual_odometry_amd import native_ops
+
+    x32, obs32, vis = scene(b, m, n, distortion, dev)
+    x64, obs64 = x32.double(), obs32.double()
+    p, mn = x32.shape[1], m * n
+    ws32 = torch.empty(native_ops.solve_workspace_bytes(b, m, n, distortion, N.DAVA_HESSIAN_COMPACT, k),
+                       dtype=torch.uint8, device=dev)
+    ws64 = torch.empty(native_ops.solve_workspace_bytes_f64(b, m, n, distortion, k), dtype=torch.uint8, device=dev)
+    kw = dict(iterations=k, error_threshold=-1.0, minimum_step=-1.0, hessian_mode=N.DAVA_HESSIAN_COMPACT)
+    runs = {"f64": lambda: native_ops.ba_solve(x64, obs64, vis, m, n, distortion, workspace=ws64, **kw),
+            "f32": lambda: native_ops.ba_solve(x32, obs32, vis, m, n, distortion, workspace=ws32, **kw)}
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {"f64": [], "f32": []}
+    for _ in range(repeats):
+        for name, fn in runs.items():
+            times[name] += timed(fn, 1)
+    lds_entries = native_ops.solve_plan(b, m, n, distortion, N.DAVA_HESSIAN_COMPACT, k)["lds_history_entries"]
+    out = {"config": tag, "batch": b, "views": m, "points": n, "distortion": distortion, "iterations": k,
+           "repeats": repeats, "device": torch.cuda.get_device_name(dev)}
+    for name, element, lds in (("f64", 8, 0), ("f32", 4, lds_entries)):
+        med = statistics.median(times[name])
+        algo = b * compact_algorithmic_bytes(p, mn, k, element, lds)
+        out[name] = {"median_s": med, "min_s": min(times[name]), "problems_per_s": b / med,
+                     "algorithmic_bytes": algo, "fraction_of_8TBps": algo / med / PEAK_BYTES_PER_S,
+                     "lds_history_entries": lds}
+    out["f64_over_f32_rate"] = out["f64"]["problems_per_s"] / out["f32"]["problems_per_s"]
+    return out
+
+
+def fused_vs_generic(tag, b, m, n, distortion, k, repeats, dev):
+    """float64 fused against the generic float64 loop around the torch closure."""
+    from deep_attention_visual_odometry_amd import BFGSSolver, ReprojectionError
+    from deep_attention_visual_odometry_amd.geometry.closure_ops import reprojection_objective
+
+    x32, obs32, vis = scene(b, m, n, distortion, dev)
+    x64, obs64 = x32.double(), obs32.double()
+    p, mn = x64.shape[1], m * n
+    solver = BFGSSolver(iterations=k, error_threshold=-1.0, minimum_step=-1.0).eval()
+    fn64 = ReprojectionError(obs64, vis, m, n, distortion)
+
+    def closure(parameters, mask):
+        return reprojection_objective(parameters, obs64[mask], vis[mask], m, n, distortion)
+
+    t_fused = timed(lambda: solver(x64, fn64), repeats)
+    assert solver.last_status is not None, "the float64 objective did not take the fused launch"
+    x_fused = solver(x64, fn64)
+    t_generic = timed(lambda: solver(x64, closure), repeats)
+    x_generic = solver(x64, closure)
+    rel = ((x_fused - x_generic).norm(dim=-1) / x_generic.norm(dim=-1)).max().item()
+    fused, generic = statistics.median(t_fused), statistics.median(t_generic)
+    algo = b * compact_algorithmic_bytes(p, mn, k, 8)
+    return {"config": tag, "batch": b, "views": m, "points": n, "distortion": distortion, "iterations": k,
+            "repeats": repeats, "device": torch.cuda.get_device_name(dev),
+            "f64_fused": {"median_s": fused, "problems_per_s": b / fused, "algorithmic_bytes": algo,
+                          "fraction_of_8TBps": algo / fused / PEAK_BYTES_PER_S},
+            "f64_generic_closure": {"median_s": generic, "problems_per_s": b / generic},
+            "fused_over_generic_rate": generic / fused, "max_rel_difference_fused_vs_generic": rel}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "f64_solve.jsonl"))
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--configs", default="c2,c3,c3_b256_k20")
+    args = ap.parse_args(argv)
+    if args.repeats < 5:
+        ap.error("--repeats must be at least 5 (the median of at least 5 timed solves)")
+    assert torch.cuda.is_available(), "measure_f64.py needs a ROCm device"
+    dev = torch.device("cuda", 0)
+    lines, ok = [], True
+    for name in args.configs.split(","):
+        if name == "c2":
+            lines.append(fused_pair("c2", 1024, 2, 128, False, 100, args.repeats, dev))
+        elif name == "c3":
+            lines.append(fused_pair("c3", 8192, 4, 256, True, 100, args.repeats, dev))
+        elif name == "c3_b256_k20":
+            line = fused_vs_generic("c3_b256_k20", 256, 4, 256, True, 20, args.repeats, dev)
+            ok = ok and line["fused_over_generic_rate"] > 1.0
+            lines.append(line)
+        else:
+            ap.error(f"unknown configuration {name!r}")
+        print(json.dumps(lines[-1]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        for line in lines:
+            fh.write(json.dumps(line) + "\n")
+    if not ok:
+        print("FAIL: the fused float64 solve is not faster than the generic float64 loop", file=sys.stderr)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
