@@ -58,7 +58,7 @@ __device__ unsigned long long g_eval_cycles[kEvalSections];
 typedef float pf2 __attribute__((ext_vector_type(2)));
 
 // ---- Taylor-branched ratios, same thresholds and series as the reference ----
-// (templated on the scalar: float, or Dual for second derivatives, dava_dual.hpp)
+// (templated on the scalar: float or double, or their dual numbers for second derivatives, dava_dual.hpp)
 // sx, cx: sin x and cos x, computed once by the caller (sincos_)
 // Constants that a float does not hold exactly (the thresholds, -1/3, the z' nudge) are written in the
 // scalar's real type R: for float and Dual the float constants they always were, for double the
@@ -224,8 +224,8 @@ __device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d,
                                         const real_t<S>* obs, const uint8_t* vis, S* grad, S* views, S* vpart,
                                         real_t<S>* scratch, int& buf, S& E_out, S& slope_out, S* obs_grad = nullptr,
                                         real_t<S>* obs_tangent_acc = nullptr, const real_t<S>* obs_dir = nullptr) {
-  using Real = real_t<S>;  // float (S = float, Dual) or double
-  static_assert(!std::is_same<S, double>::value || (PPT == 0 && !PACK), "the double objective: PPT = 0, no PACK");
+  using Real = real_t<S>;  // float (S = float, Dual) or double (S = double, DualT<double>)
+  static_assert(!std::is_same<real_t<S>, double>::value || (PPT == 0 && !PACK), "the double objective: PPT = 0, no PACK");
   constexpr int BLOCK = kWave * NW;  // threads in the workgroup
   static_assert(!DOT || (GRAD && !SLOPE), "DOT derives the slope from the reverse-mode gradient");
   static_assert(!CHECK || TRIAL, "CHECK needs a trial point");
@@ -426,7 +426,7 @@ __device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d,
       // the pair's observation; for dual numbers with an observation direction (second derivatives in the
       // observations, ba_second_order) it carries that tangent
       S ob[2] = {obs[2 * (m * N + n)], obs[2 * (m * N + n) + 1]};
-      if constexpr (std::is_same<S, Dual>::value) {
+      if constexpr (IsDual<S>::value) {
         if (obs_dir) {
           ob[0] = S(obs[2 * (m * N + n)], obs_dir[2 * (m * N + n)]);
           ob[1] = S(obs[2 * (m * N + n) + 1], obs_dir[2 * (m * N + n) + 1]);
@@ -548,7 +548,7 @@ __device__ __forceinline__ bool ba_eval(const Layout& L, const S* x, const S* d,
         ray_angle_pair<GRAD, SLOPE, S>(ra, ob, visible, p0, p1, p2, dp0, dp1, dp2, e_loc, sl_loc, gin, G0, G1, G2,
                                        go0, go1);
       }
-      if constexpr (GRAD && std::is_same<S, Dual>::value) {
+      if constexpr (GRAD && IsDual<S>::value) {
         const int pr = m * N + n;
         if (obs_grad) {
           obs_grad[2 * pr] = go0;

@@ -14,16 +14,18 @@
 //    is a full one: E, the forward-mode slope and the reverse-mode gradient at x + alpha d, so an
 //    accepted trial is the next iterate's evaluation;
 //  * every loop bounded by `iterations` or `max_line_search_trials`; no queue, no spin-wait.
-// Not here: dense / hybrid / global-vector modes, the recording tape, the drop path,
+// The recording form (dava_ba_solve_record_f64) is the same kernel behind a RECORD template flag: it
+// additionally writes dava_tape.hpp's layout in doubles (x_k, g_k at the start of every iteration, alpha_k,
+// rho_j, c_j, gamma) for the float64 adjoint (bfgs_adjoint_f64.hip); the tape's history block is its workspace.
+// Not here: dense / hybrid / global-vector modes, the drop path,
 // return_second_last, lean trials, no-move runs, on-chip history entries.
 #include "ba_objective.hpp"
+#include "dava_f64.hpp"
+#include "dava_tape.hpp"
 
 namespace dava {
 namespace f64 {
 
-constexpr long long kMaxLdsBytes = 160 * 1024;
-constexpr int kMaxIterations = 1025;  // at most 1024 history entries, as the fp32 COMPACT mode
-constexpr size_t kTailBytes = 256;    // kept for a queue counter (none is used)
 constexpr int kSolveVectors = 6;      // x d g g_prev/y s H'y
 constexpr int kEvalVectors = 3;       // x d g
 
@@ -73,6 +75,12 @@ struct SolveArgs {
   double* hist;  // B x (S[kcap][Pv], W[kcap][Pv]), or null (iterations == 1)
   double c1, c2, thr, min_step;
   int iters, max_trials, strong;
+  // RECORD: the tape's x, g and scalar blocks (B x K x Pv, B x K x Pv, B x T doubles); hist is its history block
+  double* tape_x;
+  double* tape_g;
+  double* tape_sc;
+  double* tape_tail;  // the tape's 256-byte tail (32 doubles)
+  int T;
 };
 
 template <bool GRAD, bool SLOPE, bool TRIAL, int RES>
@@ -83,7 +91,7 @@ __device__ __forceinline__ void eval(const Layout& L, const double* x, const dou
                                                                          scratch, buf, E, slope);
 }
 
-template <int RES>
+template <int RES, bool RECORD>
 __global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(SolveArgs a) {
   extern __shared__ __attribute__((aligned(16))) double lds64[];
   const Layout L = a.L;
@@ -140,6 +148,11 @@ __global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(SolveArgs 
       ++evals;
     }
     if (!(E > a.thr)) { reason = DAVA_STOP_ERROR; break; }
+    if constexpr (RECORD) {  // x_k and g_k = dE/dx(x_k) (the pads of both vectors are zero)
+      double* xr = a.tape_x + (b * a.iters + k) * Pv;
+      double* gr = a.tape_g + (b * a.iters + k) * Pv;
+      for (int i = tid; i < Pv; i += kBlock) { xr[i] = x[i]; gr[i] = g[i]; }
+    }
 
     // phi'(0) = d . g is accumulated where d is formed; its block reduction also publishes d
     double dg = 0.0;
@@ -294,6 +307,9 @@ __global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(SolveArgs 
       if (a_lo == a_hi) zoom = false;
     }
     const double alpha = a_hi;
+    if constexpr (RECORD) {
+      if (tid == 0) a.tape_sc[b * a.T + k] = alpha;
+    }
     have_next = evaluated && last_al == alpha;
     E_next = last_fa;
 
@@ -324,6 +340,28 @@ __global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(SolveArgs 
   if (a.status && tid == 0) {
     int32_t* st = a.status + b * DAVA_STATUS_WORDS;
     st[0] = steps; st[1] = reason; st[2] = evals; st[3] = trials;
+  }
+  if constexpr (RECORD) {
+    // The scalar row [alpha_0.. | rho_0.. | c_0.. | gamma]: alpha_k, k < steps, is in place (thread 0, above);
+    // rho_j, c_j of the steps - 1 entries made come from LDS.  Every slot the solve did not reach -- of the
+    // scalar row, the x / g rows and the history rows -- is zeroed: a tape is a function of its solve alone.
+    const int K = a.iters, made = steps > 1 ? steps - 1 : 0;
+    double* sc = a.tape_sc + b * a.T;
+    for (int i = steps + tid; i < a.T; i += kBlock) {
+      double v = 0.0;
+      if (i >= K && i < 2 * K) v = i - K < made ? hrho[i - K] : 0.0;
+      else if (i >= 2 * K && i < 3 * K) v = i - 2 * K < made ? hc[i - 2 * K] : 0.0;
+      else if (i == 3 * K) v = gamma0;
+      sc[i] = v;  // (i < K here: an alpha slot past the last step)
+    }
+    for (int k = steps; k < K; ++k) {
+      double* xr = a.tape_x + (b * K + k) * Pv;
+      double* gr = a.tape_g + (b * K + k) * Pv;
+      for (int i = tid; i < Pv; i += kBlock) { xr[i] = 0.0; gr[i] = 0.0; }
+    }
+    for (int j = made; j < a.kcap; ++j)
+      for (int i = tid; i < Pv; i += kBlock) { SH[(size_t)j * Pv + i] = 0.0; WH[(size_t)j * Pv + i] = 0.0; }
+    if (b == 0 && tid < (int)(kTailBytes / sizeof(double))) a.tape_tail[tid] = 0.0;
   }
 }
 
@@ -378,16 +416,6 @@ __global__ __launch_bounds__(kBlock, 1) void ba_evaluate_f64_kernel(EvalArgs a) 
     for (int i = tid; i < P; i += kBlock) a.grad[b * P + i] = g[i];
 }
 
-// DavaSceneF64 has DavaScene's fields; the shared host checks (check_scene) read no observation
-inline int check_scene_f64(const DavaSceneF64* s, bool need_data, DavaScene& as32) {
-  if (!s) return DAVA_ERR_INVALID_ARGUMENT;
-  as32 = DavaScene{s->batch,      s->num_views, s->num_points, s->distortion, s->num_parameters,
-                   reinterpret_cast<const float*>(s->observations), s->visibility, s->residual};
-  return check_scene(&as32, need_data);
-}
-
-inline int history_capacity(int iterations) { return iterations - 1 > 1 ? iterations - 1 : 1; }
-
 // DAVA_OK if the solve runs this scene / config (host-only)
 inline int solve_supported(const DavaScene& sc, const DavaSolverConfigF64* c) {
   if (!c || c->iterations < 0 || c->max_line_search_trials < 0) return DAVA_ERR_INVALID_ARGUMENT;
@@ -427,9 +455,11 @@ extern "C" size_t dava_ba_solve_workspace_bytes_f64(const DavaSceneF64* scene, c
   return f64::history_bytes(sc, config->iterations) + f64::kTailBytes;
 }
 
-extern "C" int dava_ba_solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0,
-                                 double* x_out, double* error_out, int32_t* status_out, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
+// dava_ba_solve_f64 (tape == nullptr: `workspace` holds the history rows) and dava_ba_solve_record_f64
+// (`workspace` is the tape, whose first block is the history rows)
+static int solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0, double* x_out,
+                     double* error_out, int32_t* status_out, void* workspace, size_t workspace_bytes, bool record,
+                     void* stream) {
   DavaScene sc;
   const int st = f64::check_scene_f64(scene, true, sc);
   if (st != DAVA_OK) return st;
@@ -438,10 +468,15 @@ extern "C" int dava_ba_solve_f64(const DavaSceneF64* scene, const DavaSolverConf
   if (sc.batch == 0) return DAVA_OK;
   if (!x0 || !x_out) return DAVA_ERR_INVALID_ARGUMENT;
   if (sup != DAVA_OK) return sup;
-  const bool uses_ws = config->iterations > 1;
-  // (the size the query reports, tail included: a queue counter put there later finds its bytes)
-  if (uses_ws && (!workspace || workspace_bytes < f64::history_bytes(sc, config->iterations) + f64::kTailBytes))
+  const bool uses_ws = record || config->iterations > 1;
+  const TapeLayout tl = tape_layout_f64(sc.batch, sc.num_parameters, config->iterations);
+  if (record) {
+    if (!status_out) return DAVA_ERR_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < tl.total_bytes) return DAVA_ERR_WORKSPACE;
+  } else if (uses_ws && (!workspace || workspace_bytes < f64::history_bytes(sc, config->iterations) + f64::kTailBytes)) {
+    // (the size the query reports, tail included: a queue counter put there later finds its bytes)
     return DAVA_ERR_WORKSPACE;
+  }
   f64::SolveArgs a;
   a.L = make_layout(&sc);
   a.B = sc.batch;
@@ -461,18 +496,42 @@ extern "C" int dava_ba_solve_f64(const DavaSceneF64* scene, const DavaSolverConf
   a.iters = config->iterations;
   a.max_trials = config->max_line_search_trials;
   a.strong = config->strong_wolfe;
+  a.tape_x = record ? static_cast<double*>(workspace) + tl.x : nullptr;
+  a.tape_g = record ? static_cast<double*>(workspace) + tl.g : nullptr;
+  a.tape_sc = record ? static_cast<double*>(workspace) + tl.scal : nullptr;
+  a.tape_tail = record ? static_cast<double*>(workspace) + tl.vecs : nullptr;
+  a.T = tl.T;
   const int lds = (int)f64::carve(sc.num_views, sc.num_points, a.Pv, a.kcap).total_bytes;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (sc.residual == DAVA_RESIDUAL_RAY_ANGLE) {
-    const auto kernel = f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_RAY_ANGLE>;
+  auto go = [&](auto kernel) {
     set_dynamic_lds(kernel, lds);
     hipLaunchKernelGGL(kernel, dim3(a.B), dim3(kBlock), lds, s, a);
-  } else {
-    const auto kernel = f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_SQUARED_REPROJECTION>;
-    set_dynamic_lds(kernel, lds);
-    hipLaunchKernelGGL(kernel, dim3(a.B), dim3(kBlock), lds, s, a);
-  }
+  };
+  const bool ray = sc.residual == DAVA_RESIDUAL_RAY_ANGLE;
+  if (ray && record) go(f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_RAY_ANGLE, true>);
+  else if (ray) go(f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_RAY_ANGLE, false>);
+  else if (record) go(f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_SQUARED_REPROJECTION, true>);
+  else go(f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_SQUARED_REPROJECTION, false>);
   return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+}
+
+extern "C" int dava_ba_solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0,
+                                 double* x_out, double* error_out, int32_t* status_out, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  return solve_f64(scene, config, x0, x_out, error_out, status_out, workspace, workspace_bytes, false, stream);
+}
+
+extern "C" size_t dava_ba_solve_tape_bytes_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config) {
+  DavaScene sc;
+  if (f64::check_scene_f64(scene, false, sc) != DAVA_OK) return 0;
+  if (f64::solve_supported(sc, config) != DAVA_OK) return 0;
+  return tape_layout_f64(sc.batch, sc.num_parameters, config->iterations).total_bytes;
+}
+
+extern "C" int dava_ba_solve_record_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0,
+                                        double* x_out, double* error_out, int32_t* status_out, void* tape,
+                                        size_t tape_bytes, void* stream) {
+  return solve_f64(scene, config, x0, x_out, error_out, status_out, tape, tape_bytes, true, stream);
 }
 
 extern "C" int dava_ba_evaluate_f64(const DavaSceneF64* scene, const double* x, const double* direction,

@@ -44,4 +44,14 @@ inline TapeLayout tape_layout(int B, int P, int K, int vec_floats = 0) {
   return t;
 }
 
+// The float64 recording (dava_ba_solve_record_f64): the same blocks and offsets in ELEMENTS, every element a
+// double, no vecs block (the float64 solve has no global-vector mode).  A function of its own, so the
+// float32 layout above is untouched.
+inline TapeLayout tape_layout_f64(int B, int P, int K) {
+  TapeLayout t = tape_layout(B, P, K, 0);
+  t.queue_byte = t.vecs * sizeof(double);
+  t.total_bytes = t.queue_byte + 256;
+  return t;
+}
+
 }  // namespace dava

@@ -117,6 +117,17 @@ SIGNATURES = {
     "dava_ba_solve_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSolverConfigF64), _vp, _vp,
                                          _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dava_ba_evaluate_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # float64 second derivatives, recording solve and adjoint
+    "dava_ba_second_order_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64)] + [_vp] * 9),
+    "dava_ba_solve_tape_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                       ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_record_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSolverConfigF64),
+                                                _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dava_ba_solve_backward_workspace_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                                     ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_backward_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSolverConfigF64),
+                                                  _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                                  _vp]),
     "dava_ba_second_order": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 8),
     "dava_ba_second_order_obs": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 9),
     "dava_ba_solve_tape_bytes": (ctypes.c_size_t, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSolverConfig)]),

@@ -27,7 +27,10 @@ cross term, csrc/ba_second_order.hip), so gradients reach captured observations.
 float64: an objective built from float64 device observations also solves float64 parameters in one launch
 (``dava_ba_solve_f64``: compact history, eval-mode semantics, no graph); what that kernel does not cover
 (dense mode, more than 1025 iterations, training mode's drop path) runs the generic loop with the float64
-objective as its closure, and float64 parameters that require grad raise ``TypeError``.
+objective as its closure.  float64 parameters that require grad raise ``TypeError`` unless the objective was
+built with ``float64_derivatives=True``: then the solve is differentiated by the recording float64 solve and
+its adjoint kernel (``dava_ba_solve_record_f64`` / ``dava_ba_solve_backward_f64``), or by the generic loop
+with torch's graph where those do not apply (dense mode, the GENERIC_BACKWARD override, training mode).
 
 Training mode's ``return_second_last`` runs fused too (a problem stopped by the minimum-step rule
 keeps x before its last step); when the reference's scatter would have moved rows between problems
@@ -235,8 +238,11 @@ class BFGSSolver(Module):
         """float64 parameters on an objective built from float64 device observations: one launch of
         ``dava_ba_solve_f64`` (compact history, eval-mode semantics) where it applies, else the generic loop
         with the objective as its closure (its float64 value and first derivative are HIP kernels too).
-        Differentiating through a float64 solve is not available: second derivatives are float32 only."""
-        if parameters.requires_grad:
+        Differentiating through a float64 solve needs an objective built with ``float64_derivatives=True``
+        (without it: ``TypeError``, second derivatives are float32 only): the recording float64 solve and its
+        adjoint kernel (``dava_ba_solve_record_f64`` / ``dava_ba_solve_backward_f64``) where they apply and the
+        GENERIC_BACKWARD override is off, else the generic loop with the graph kept by torch."""
+        if parameters.requires_grad and not fn.float64_derivatives:
             raise TypeError("differentiating through a float64 solve needs second derivatives of the fused "
                             "objectives, which are float32 only")
         lead = parameters.shape[:-1]
@@ -247,6 +253,19 @@ class BFGSSolver(Module):
                  and 1 <= num_iterations <= self.MAX_COMPACT_ENTRIES + 1
                  and native_ops.solve_workspace_bytes_f64(max(x0.shape[0], 1), fn.num_views, fn.num_points,
                                                           fn.distortion, num_iterations, fn.residual) > 0)
+        if parameters.requires_grad:  # the solve is a graph node only when the parameters require grad
+            fused = (fused and not _native.python_knob("GENERIC_BACKWARD")
+                     and native_ops.solve_tape_supported_f64(max(x0.shape[0], 1), fn.num_views, fn.num_points,
+                                                             fn.distortion, num_iterations, fn.residual))
+            if fused:
+                x, status = native_ops.ba_solve_differentiable_f64(
+                    x0, fn.observations64.reshape(-1, fn.num_views, fn.num_points, 2),
+                    fn.visibility.reshape(-1, fn.num_views, fn.num_points), fn.num_views, fn.num_points,
+                    fn.distortion, sufficient_decrease=self.sufficient_decrease, curvature=self.curvature,
+                    error_threshold=error_threshold, iterations=num_iterations, minimum_step=self.minimum_step,
+                    residual=fn.residual)
+                self.last_status = status
+                return x.reshape(parameters.shape)
         if not fused:
             self.last_status = None  # the generic loop has no status words
             self._check_generic_fits(parameters, num_iterations, second_last)

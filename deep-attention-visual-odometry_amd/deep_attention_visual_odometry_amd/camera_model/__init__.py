@@ -51,6 +51,11 @@ _F64_FIRST_ORDER_ONLY = ("the float64 fused objectives give E and dE/dx only: se
                          "observation gradient are float32 only")
 
 
+def _second_order(x):
+    """The forward-over-reverse launch of x's dtype (float64 only on objectives built with float64_derivatives)."""
+    return native_ops.ba_second_order_f64 if x.dtype == torch.float64 else native_ops.ba_second_order
+
+
 class _NativeObjective(torch.autograd.Function):
     """E(x, obs) per row from the HIP objective kernel.  Its backward is itself
     differentiable (``_NativeGradient``), so ``torch.autograd.grad(..., create_graph=True)``
@@ -58,19 +63,19 @@ class _NativeObjective(torch.autograd.Function):
     derivatives from the forward-over-reverse kernel (``dava_ba_second_order``)."""
 
     @staticmethod
-    def forward(ctx, x, observations, visibility, num_views, num_points, distortion, residual):
+    def forward(ctx, x, observations, visibility, num_views, num_points, distortion, residual, f64_derivatives=False):
         need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if need_obs and x.dtype == torch.float64:
+        if need_obs and x.dtype == torch.float64 and not f64_derivatives:
             raise TypeError(_F64_FIRST_ORDER_ONLY + " (the observations require grad)")
         if need_obs:  # dE/dobs comes from the second-order kernel (v = 0)
-            err, grad, _, obs_grad, _ = native_ops.ba_second_order(
+            err, grad, _, obs_grad, _ = _second_order(x)(
                 x, observations, visibility, num_views, num_points, distortion, residual=residual, want_hv=False)
         else:
             err, grad, _ = native_ops.ba_evaluate(x, observations, visibility, num_views, num_points, distortion,
                                                   want_grad=need_x, residual=residual)
             obs_grad = None
         ctx.save_for_backward(x, observations, visibility)
-        ctx.meta = (num_views, num_points, distortion, residual)
+        ctx.meta = (num_views, num_points, distortion, residual, f64_derivatives)
         ctx.first = (grad, obs_grad)
         return err
 
@@ -78,7 +83,7 @@ class _NativeObjective(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, obs, vis = ctx.saved_tensors
         need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if torch.is_grad_enabled() and x.dtype == torch.float64:
+        if torch.is_grad_enabled() and x.dtype == torch.float64 and not ctx.meta[4]:
             raise TypeError(_F64_FIRST_ORDER_ONLY + " (create_graph)")
         if torch.is_grad_enabled():  # create_graph: keep the gradient differentiable
             grad, obs_grad = _NativeGradient.apply(x, obs, vis, *ctx.meta)
@@ -86,7 +91,7 @@ class _NativeObjective(torch.autograd.Function):
             grad, obs_grad = ctx.first
         gx = grad_out.unsqueeze(-1) * grad if need_x else None
         gobs = grad_out[:, None, None, None] * obs_grad if (need_obs and obs_grad is not None) else None
-        return gx, gobs, None, None, None, None, None
+        return gx, gobs, None, None, None, None, None, None
 
 
 class _NativeGradient(torch.autograd.Function):
@@ -94,8 +99,10 @@ class _NativeGradient(torch.autograd.Function):
     u is (H u, (d2E/dobs dx) u), from one forward-over-reverse launch."""
 
     @staticmethod
-    def forward(ctx, x, observations, visibility, num_views, num_points, distortion, residual):
-        _, grad, _, obs_grad, _ = native_ops.ba_second_order(
+    def forward(ctx, x, observations, visibility, num_views, num_points, distortion, residual, f64_derivatives=False):
+        if x.dtype == torch.float64 and not f64_derivatives:
+            raise TypeError(_F64_FIRST_ORDER_ONLY)
+        _, grad, _, obs_grad, _ = _second_order(x)(
             x, observations, visibility, num_views, num_points, distortion, residual=residual, want_hv=False)
         ctx.save_for_backward(x, observations, visibility)
         ctx.meta = (num_views, num_points, distortion, residual)
@@ -108,13 +115,12 @@ class _NativeGradient(torch.autograd.Function):
         # u_obs: a cotangent on dE/dobs (differentiating it again): the observations carry it as a tangent in
         # the same forward-over-reverse launch (dava_ba_second_order_obs)
         if u is None and u_obs is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         x, obs, vis = ctx.saved_tensors
-        _, _, hv, _, obs_hv = native_ops.ba_second_order(x, obs, vis, *ctx.meta[:3], direction=u,
-                                                          residual=ctx.meta[3],
-                                                          want_obs=ctx.needs_input_grad[1], obs_direction=u_obs)
+        _, _, hv, _, obs_hv = _second_order(x)(x, obs, vis, *ctx.meta[:3], direction=u, residual=ctx.meta[3],
+                                               want_obs=ctx.needs_input_grad[1], obs_direction=u_obs)
         return (hv if ctx.needs_input_grad[0] else None, obs_hv if ctx.needs_input_grad[1] else None,
-                None, None, None, None, None)
+                None, None, None, None, None, None)
 
 
 class ReprojectionError:
@@ -124,13 +130,16 @@ class ReprojectionError:
 
     observations: (B..., M, N, 2) float32, visibility: (B..., M, N) bool/0-1,
     on the same ROCm device as the parameters.  float64 device observations also enable the float64
-    kernels: float64 parameters then evaluate and solve in float64 (value and first derivative only).  With ``distortion=True`` the
+    kernels: float64 parameters then evaluate and solve in float64 (value and first derivative only;
+    ``float64_derivatives=True`` -- float64 device observations required, else ``ValueError`` -- adds the float64
+    second derivatives: create_graph, observations that require grad, double backward of dE/dobs, and the
+    drop-in solver differentiates through a float64 solve).  With ``distortion=True`` the
     five Brown-Conrady coefficients (k1 k2 k3 p1 p2) are appended to the
     parameter vector (``camera_model/distorted_camera_model.py:59-86``).
     """
 
     def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int,
-                 distortion: bool = False):
+                 distortion: bool = False, float64_derivatives: bool = False):
         if observations.shape[-3:] != (num_views, num_points, 2):
             raise ValueError(f"observations must end in ({num_views}, {num_points}, 2), got {tuple(observations.shape)}")
         if visibility.shape != observations.shape[:-1]:
@@ -144,6 +153,11 @@ class ReprojectionError:
         # objective stays float32 only, as before.
         self.observations64 = (observations if observations.device.type != "cpu"
                                and observations.dtype == torch.float64 else None)
+        # opt-in: the float64 second derivatives (dava_ba_second_order_f64) and, through them, the float64 adjoint
+        self.float64_derivatives = bool(float64_derivatives)
+        if self.float64_derivatives and self.observations64 is None:
+            raise ValueError("float64_derivatives=True needs float64 observations on a ROCm device "
+                             f"(got {observations.dtype} on {observations.device})")
         self.visibility = visibility.to(torch.uint8)
         self.num_views = int(num_views)
         self.num_points = int(num_points)
@@ -180,7 +194,8 @@ class ReprojectionError:
             return self._torch_objective(x, obs.to(x.dtype), vis).reshape(lead)
         if x.dtype not in (torch.float32, torch.float64):
             raise TypeError("ReprojectionError evaluates in float32 (or float64, built from float64 observations)")
-        err = _NativeObjective.apply(x, obs, vis, self.num_views, self.num_points, self.distortion, self.residual)
+        err = _NativeObjective.apply(x, obs, vis, self.num_views, self.num_points, self.distortion, self.residual,
+                                     self.float64_derivatives and use64)
         return err.reshape(lead)
 
 
@@ -205,8 +220,10 @@ class RayAngleError(ReprojectionError):
 
     residual = native_ops.N.DAVA_RESIDUAL_RAY_ANGLE
 
-    def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int):
-        super().__init__(observations, visibility, num_views, num_points, distortion=False)
+    def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int,
+                 float64_derivatives: bool = False):
+        super().__init__(observations, visibility, num_views, num_points, distortion=False,
+                         float64_derivatives=float64_derivatives)
 
     def _torch_objective(self, x, obs, vis):
         from ..geometry.closure_ops import ray_angle_objective

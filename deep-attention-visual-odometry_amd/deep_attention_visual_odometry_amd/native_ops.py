@@ -82,6 +82,30 @@ def ba_second_order(x: torch.Tensor, observations: torch.Tensor, visibility: tor
             obs_hv if (want_obs and want_hv) else None)
 
 
+def _f64_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
+    N.require_device_tensor(x, what)
+    if x.dtype != torch.float64:
+        raise TypeError(f"the float64 entry points take float64 tensors, got {x.dtype} for {what}")
+    return _c(x.detach())
+
+
+def ba_second_order_f64(x: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
+                        num_points: int, distortion: bool = False, direction: Optional[torch.Tensor] = None,
+                        residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, want_hv: bool = True,
+                        want_obs: bool = True, obs_direction: Optional[torch.Tensor] = None):
+    """:func:`ba_second_order` for a (B, P) float64 batch with float64 observations
+    (``torch.ops.dava.ba_second_order_f64``, dual numbers over double)."""
+    x = _f64_on_device(x, "x")
+    obs, vis = _scene_inputs(x, observations, visibility)
+    if obs_direction is not None:
+        obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=torch.float64)).reshape(obs.shape)
+    err, grad, hv, obs_grad, obs_hv = torch.ops.dava.ba_second_order_f64(
+        x, obs, vis, num_views, num_points, bool(distortion), _opt(direction, torch.float64), int(residual),
+        bool(want_hv), bool(want_obs), obs_direction)
+    return (err, grad, hv if want_hv else None, obs_grad if want_obs else None,
+            obs_hv if (want_obs and want_hv) else None)
+
+
 def ba_solve(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
              num_points: int, distortion: bool, *, sufficient_decrease: float = 1e-4, curvature: float = 0.9,
              error_threshold: float = 1e-4, iterations: int = 1000, minimum_step: float = 1e-8,
@@ -190,6 +214,67 @@ def ba_solve_differentiable(x0: torch.Tensor, observations: torch.Tensor, visibi
     cfg = (sufficient_decrease, curvature, error_threshold, iterations, minimum_step, max_line_search_trials, strong,
            drop_path_p, drop_seed, return_second_last)
     return _FusedSolve.apply(x0, observations, visibility, num_views, num_points, distortion, residual, cfg)
+
+
+def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+                             residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> bool:
+    """Host-only: does this shape have the float64 fused adjoint -- a recording forward
+    (``dava_ba_solve_tape_bytes_f64`` > 0) AND a backward that can launch on it
+    (``dava_ba_solve_backward_workspace_bytes_f64`` > 0)?"""
+    from ._ops import scene_struct_f64, solver_config_f64
+
+    lib = N.load_library()
+    sc = scene_struct_f64(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
+    cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
+    return (int(lib.dava_ba_solve_tape_bytes_f64(sc, cfg)) > 0
+            and int(lib.dava_ba_solve_backward_workspace_bytes_f64(sc, cfg)) > 0)
+
+
+class _FusedSolveF64(torch.autograd.Function):
+    """:class:`_FusedSolve` in float64: the recording float64 solve (``dava_ba_solve_record_f64``) and its adjoint
+    kernel (csrc/bfgs_adjoint_f64.hip).  Eval-mode semantics only.  Not differentiable twice."""
+
+    @staticmethod
+    def forward(ctx, x0, observations, visibility, num_views, num_points, distortion, residual, cfg):
+        c1, c2, thr, iters, min_step, trials, strong = cfg
+        x0c = _f64_on_device(x0, "parameters")
+        obs, vis = _scene_inputs(x0c, observations, visibility)
+        x, status, tape, _ = torch.ops.dava.ba_solve_record_f64(
+            x0c, obs, vis, int(num_views), int(num_points), bool(distortion), float(c1), float(c2), float(thr),
+            int(iters), float(min_step), int(trials), bool(strong), int(residual), False)
+        ctx.save_for_backward(tape, status, obs, vis)
+        ctx.meta = (int(num_views), int(num_points), bool(distortion), int(iters), int(residual))
+        ctx.mark_non_differentiable(status)
+        ctx.recorded = torch.cuda.Event()  # the tape is complete once the recording launch is
+        ctx.recorded.record(torch.cuda.current_stream(x0c.device))
+        return x, status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, x_grad, _status_grad):
+        tape, status, obs, vis = ctx.saved_tensors
+        m, n, dist, iters, residual = ctx.meta
+        need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if x_grad is None:
+            return (None,) * 8
+        # autograd may run this backward on another stream than the recording launch's: order the
+        # adjoint after the tape is written
+        torch.cuda.current_stream(tape.device).wait_event(ctx.recorded)
+        gx, gobs = torch.ops.dava.ba_solve_backward_f64(_c(x_grad.to(torch.float64)), tape, status, obs, vis, m, n,
+                                                        dist, iters, residual, bool(need_obs))
+        return (gx if need_x else None, gobs if need_obs else None, None, None, None, None, None, None)
+
+
+def ba_solve_differentiable_f64(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor,
+                                num_views: int, num_points: int, distortion: bool, *,
+                                sufficient_decrease: float = 1e-4, curvature: float = 0.9,
+                                error_threshold: float = 1e-4, iterations: int = 1000, minimum_step: float = 1e-8,
+                                max_line_search_trials: int = 1000, strong: bool = True,
+                                residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION):
+    """The float64 fused solve as an autograd node w.r.t. x0 and the (float64) observations.
+    Returns (x, status)."""
+    cfg = (sufficient_decrease, curvature, error_threshold, iterations, minimum_step, max_line_search_trials, strong)
+    return _FusedSolveF64.apply(x0, observations, visibility, num_views, num_points, distortion, residual, cfg)
 
 
 def solve_workspace_bytes(batch: int, num_views: int, num_points: int, distortion: bool,

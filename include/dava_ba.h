@@ -23,7 +23,8 @@
  *    dava_status_string() turns a code into text.
  *  - fp32 throughout the fused solver (the reference's dtype for the BA path),
  *    with an opt-in float64 flavour of the objective evaluation and of the
- *    one-launch COMPACT solve (the `_f64` entry points on DavaSceneF64: the
+ *    one-launch COMPACT solve, its second derivatives and its adjoint (the
+ *    `_f64` entry points on DavaSceneF64: the
  *    reference's training entry point and its solver / geometry tests run in
  *    float64); the generic BFGS building blocks come in _f32 and _f64 flavours
  *    because the reference's own unit tests drive them in float64.
@@ -199,9 +200,10 @@ int dava_ba_evaluate(const DavaScene* scene, const float* x, const float* direct
 /* ---- float64 flavour of the evaluation and of the fused solve (additive to ABI 4) ----
  * The same objectives and the same algorithm with every value a double: parameters, observations,
  * thresholds (1e-4 as a double is the reference's 1e-4), history rows.  COMPACT inverse Hessian only,
- * eval mode only (no drop path, no return_second_last, no tape), one 256-thread workgroup per problem
- * with its whole state in LDS: a shape is supported when that image fits 160 KiB (C1-C3 do; C5 does
- * not) and 1 <= iterations <= 1025.  Anything else: DAVA_ERR_UNSUPPORTED, and 0 from the size query. */
+ * eval mode only (no drop path, no return_second_last; the tape: dava_ba_solve_record_f64 below), one
+ * 256-thread workgroup per problem with its whole state in LDS: a shape is supported when that image
+ * fits 160 KiB (C1-C3 do; C5 does not) and 1 <= iterations <= 1025.  Anything else:
+ * DAVA_ERR_UNSUPPORTED, and 0 from the size query. */
 typedef struct DavaSceneF64 {
   int32_t batch;               /* B >= 0                               */
   int32_t num_views;           /* M >= 2                               */
@@ -238,6 +240,40 @@ int dava_ba_solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* conf
 /* dava_ba_evaluate in float64 (same NULL conventions). */
 int dava_ba_evaluate_f64(const DavaSceneF64* scene, const double* x, const double* direction, const double* alpha,
                          double* error_out, double* grad_out, double* slope_out, void* stream);
+
+/* ---- float64 second derivatives and the float64 adjoint of the fused solve (additive to ABI 4) ----
+ * dava_ba_second_order_obs in float64: forward-over-reverse with dual numbers over double, one 256-thread
+ * workgroup per problem, the dual image in LDS (DAVA_ERR_UNSUPPORTED past 160 KiB).  Per problem, with a
+ * parameter direction v and an observation direction u (either NULL = 0):
+ *   error_out (B) E, grad_out (B, P) dE/dx, hv_out (B, P) H v + (d2E/dx dobs) u,
+ *   obs_grad_out (B, M, N, 2) dE/dobs, obs_hv_out (B, M, N, 2) (d2E/dobs dx) v + (d2E/dobs2) u.
+ * Every output may be NULL. */
+int dava_ba_second_order_f64(const DavaSceneF64* scene, const double* x, const double* direction,
+                             const double* obs_direction, double* error_out, double* grad_out, double* hv_out,
+                             double* obs_grad_out, double* obs_hv_out, void* stream);
+
+/* Bytes of the float64 tape: csrc/dava_tape.hpp's blocks with every element a double,
+ *   8 * B * (2 kcap Pv + 2 K Pv + round_up(3 K + 1, 4)) + 256,  K = iterations, kcap = max(K - 1, 1),
+ *   Pv = round_up(P, 4).
+ * > 0 exactly where dava_ba_solve_workspace_bytes_f64 is. */
+size_t dava_ba_solve_tape_bytes_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config);
+
+/* dava_ba_solve_f64 (bitwise the same x_out, error_out and status_out) that also writes the tape: x_k and g_k
+ * at the start of every iteration, alpha_k, rho_j, c_j and gamma; the tape's history block is the solve's
+ * workspace.  Slots the solve does not reach are zeroed.  status_out is required. */
+int dava_ba_solve_record_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0,
+                             double* x_out, double* error_out, int32_t* status_out, void* tape, size_t tape_bytes,
+                             void* stream);
+
+/* Device workspace of dava_ba_solve_backward_f64 (the adjoint's rows, 8 * B * K * Pv, and a 256-byte tail),
+ * or 0 where it does not run: its LDS image (14 vectors of Pv doubles, the scene) must fit 160 KiB. */
+size_t dava_ba_solve_backward_workspace_bytes_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config);
+
+/* dava_ba_solve_backward in float64: x_out_grad (B, P) -> x0_grad (B, P), observations_grad (B, M, N, 2) or
+ * NULL.  One workgroup per problem, deterministic (two launches give bitwise the same gradients). */
+int dava_ba_solve_backward_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const void* tape,
+                               size_t tape_bytes, const int32_t* status, const double* x_out_grad, double* x0_grad,
+                               double* observations_grad, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Second derivatives of the objective, for differentiating THROUGH a solve whose error
  * function is a fused objective (the reference's create_graph double backward,

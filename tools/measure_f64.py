@@ -7,6 +7,13 @@ generic float64 loop, one JSON line per configuration (default: profiles/f64_sol
   c3_b256_k20    C3 at B = 256, K = 20: float64 fused against the only float64 route there was before it, the
                  drop-in's generic loop around the torch closure (geometry.closure_ops) in float64.
 
+--mode grad (default output profiles/f64_adjoint.jsonl): solve PLUS gradient, d (w . x_K) / d (x0, observations):
+  c2, c3         the float64 recording solve + adjoint (dava_ba_solve_record_f64, dava_ba_solve_backward_f64)
+                 and the float32 recording solve + adjoint at the same shapes, K = 100, alternated in one process.
+  c3_b32_k20     C3 at B = 32, K = 20 (a batch whose dense graph, about 3 K P^2 8 bytes per problem, fits): the
+                 float64 fused route against the generic float64 loop with torch's graph (GENERIC_BACKWARD).
+  No rate is a requirement in this mode: the numbers are reported as measured.
+
 Timing: device events around each solve, every shape warmed up first, median of --repeats (>= 5) solves.
 Reported: problems/s, algorithmic HBM bytes (bench.py's compact model; 8-byte elements for float64, computed
 here), the fraction of 8 TB/s they amount to, and the ratio to the fp32 fused rate.  The one requirement
@@ -124,19 +131,110 @@ def fused_vs_generic(tag, b, m, n, distortion, k, repeats, dev):
             "fused_over_generic_rate": generic / fused, "max_rel_difference_fused_vs_generic": rel}
 
 
+def grad_pair(tag, b, m, n, distortion, k, repeats, dev):
+    """Solve + backward, float64 and float32 fused (recording solve + adjoint kernel), alternated run by run."""
+    from deep_attention_visual_odometry_amd import native_ops
+
+    x32, obs32, vis = scene(b, m, n, distortion, dev)
+    w32 = torch.randn(x32.shape, generator=torch.Generator().manual_seed(1)).to(dev)
+    kw = dict(iterations=k, error_threshold=-1.0, minimum_step=-1.0)
+    marks = {}
+
+    def run(name, solve, x, obs, w):
+        xg, og = x.clone().requires_grad_(True), obs.clone().requires_grad_(True)
+        start, mid, end = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        start.record()
+        out, status = solve(xg, og, vis, m, n, distortion, **kw)
+        mid.record()
+        gx, go = torch.autograd.grad((out * w).sum(), [xg, og])
+        end.record()
+        end.synchronize()
+        finite = (torch.isfinite(gx).all(dim=-1) & (status[:, 0] == k)).float().mean().item()
+        marks[name] = (start.elapsed_time(mid) * 1e-3, mid.elapsed_time(end) * 1e-3, finite)
+
+    runs = {"f64": lambda: run("f64", native_ops.ba_solve_differentiable_f64, x32.double(), obs32.double(),
+                               w32.double()),
+            "f32": lambda: run("f32", native_ops.ba_solve_differentiable, x32, obs32, w32)}
+    for fn in runs.values():  # warm-up of both (module load, allocator)
+        fn()
+    torch.cuda.synchronize()
+    times = {"f64": [], "f32": []}
+    for _ in range(repeats):
+        for name, fn in runs.items():
+            fn()
+            times[name].append(marks[name])
+    out = {"config": "grad_" + tag, "batch": b, "views": m, "points": n, "distortion": distortion, "iterations": k,
+           "repeats": repeats, "device": torch.cuda.get_device_name(dev)}
+    for name in ("f64", "f32"):
+        fwd = statistics.median(t[0] for t in times[name])
+        bwd = statistics.median(t[1] for t in times[name])
+        total = statistics.median(t[0] + t[1] for t in times[name])
+        out[name] = {"median_s": total, "recording_solve_median_s": fwd, "backward_median_s": bwd,
+                     "problems_per_s": b / total,
+                     "fraction_of_problems_with_k_steps_and_finite_gradients": times[name][-1][2]}
+    out["f64_over_f32_rate"] = out["f64"]["problems_per_s"] / out["f32"]["problems_per_s"]
+    return out
+
+
+def grad_vs_generic(tag, b, m, n, distortion, k, repeats, dev):
+    """Solve + backward in float64 through the drop-in: the fused route against the generic loop with torch's graph."""
+    from deep_attention_visual_odometry_amd import BFGSSolver, ReprojectionError, _native
+
+    x32, obs32, vis = scene(b, m, n, distortion, dev)
+    x64, obs64 = x32.double(), obs32.double()
+    w = torch.randn(x64.shape, generator=torch.Generator().manual_seed(1), dtype=torch.float64).to(dev)
+    solver = BFGSSolver(iterations=k, error_threshold=-1.0, minimum_step=-1.0).eval()
+    grads = {}
+
+    def run(name):
+        xg, og = x64.clone().requires_grad_(True), obs64.clone().requires_grad_(True)
+        out = solver(xg, ReprojectionError(og, vis, m, n, distortion, float64_derivatives=True))
+        grads[name] = torch.autograd.grad((out * w).sum(), [xg, og])
+        assert (solver.last_status is not None) == (name == "fused")
+
+    t_fused = timed(lambda: run("fused"), repeats)
+    with _native.debug_overrides(GENERIC_BACKWARD=1):
+        t_generic = timed(lambda: run("generic"), repeats)
+    rel = [((a - c).reshape(b, -1).norm(dim=-1) / c.reshape(b, -1).norm(dim=-1)).max().item()
+           for a, c in zip(grads["fused"], grads["generic"])]
+    fused, generic = statistics.median(t_fused), statistics.median(t_generic)
+    return {"config": "grad_" + tag, "batch": b, "views": m, "points": n, "distortion": distortion, "iterations": k,
+            "repeats": repeats, "device": torch.cuda.get_device_name(dev),
+            "f64_fused": {"median_s": fused, "problems_per_s": b / fused},
+            "f64_generic_graph": {"median_s": generic, "problems_per_s": b / generic},
+            "fused_over_generic_rate": generic / fused,
+            "max_rel_difference_fused_vs_generic": {"x0_grad": rel[0], "observations_grad": rel[1]}}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "f64_solve.jsonl"))
+    ap.add_argument("--mode", choices=("solve", "grad"), default="solve",
+                    help="solve: the solve alone (the default); grad: solve plus gradient")
+    ap.add_argument("--out", default=None,
+                    help="default: profiles/f64_solve.jsonl (solve), profiles/f64_adjoint.jsonl (grad)")
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--configs", default="c2,c3,c3_b256_k20")
+    ap.add_argument("--configs", default=None, help="default: c2,c3,c3_b256_k20 (solve), c2,c3,c3_b32_k20 (grad)")
     args = ap.parse_args(argv)
+    grad = args.mode == "grad"
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "f64_adjoint.jsonl" if grad else "f64_solve.jsonl")
+    if args.configs is None:
+        args.configs = "c2,c3,c3_b32_k20" if grad else "c2,c3,c3_b256_k20"
     if args.repeats < 5:
         ap.error("--repeats must be at least 5 (the median of at least 5 timed solves)")
     assert torch.cuda.is_available(), "measure_f64.py needs a ROCm device"
     dev = torch.device("cuda", 0)
     lines, ok = [], True
     for name in args.configs.split(","):
-        if name == "c2":
+        if grad and name == "c2":
+            lines.append(grad_pair("c2", 1024, 2, 128, False, 100, args.repeats, dev))
+        elif grad and name == "c3":
+            lines.append(grad_pair("c3", 8192, 4, 256, True, 100, args.repeats, dev))
+        elif grad and name == "c3_b32_k20":
+            lines.append(grad_vs_generic("c3_b32_k20", 32, 4, 256, True, 20, args.repeats, dev))
+        elif grad:
+            ap.error(f"unknown configuration {name!r} for --mode grad")
+        elif name == "c2":
             lines.append(fused_pair("c2", 1024, 2, 128, False, 100, args.repeats, dev))
         elif name == "c3":
             lines.append(fused_pair("c3", 8192, 4, 256, True, 100, args.repeats, dev))
