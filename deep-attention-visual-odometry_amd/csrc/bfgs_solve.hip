@@ -68,19 +68,7 @@ struct SolveArgs {
   int second_last;  // training mode's return_second_last: a minimum-step stop keeps x_k
 };
 
-// Training mode's drop path (bfgs_solver.py:121-125): problem b keeps updating at iteration k iff
-// u(seed, b, k) > p, u uniform on [0, 1) with 24-bit resolution from a counter-based 64-bit mix
-// (splitmix64's finaliser over the packed counter): no state, any launch shape or work-queue
-// order draws the same schedule.
-__device__ __forceinline__ float drop_uniform(unsigned long long seed, int b, int k) {
-  unsigned long long z = seed ^ (((unsigned long long)(unsigned)b << 32) | (unsigned)k);
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
-
+// (Training mode's drop path draws drop_uniform, dava_common.hpp.)
 // Trial slopes phi'(alpha) of the full trials (the ones that also form the gradient): forward mode (a JVP
 // riding on the trial's evaluation) in LDS mode, where the reverse-mode form d . grad measured -1% at C3
 // (profiles/r01b_ab_variants.log, `dot`); d . grad in global-vector mode, where it saves the pair sweep's

@@ -1,5 +1,5 @@
 // The float64 flavour of the BA hot path on gfx950: objective evaluation (dava_ba_evaluate_f64) and the
-// one-launch eval-mode BFGS + strong-Wolfe solve (dava_ba_solve_f64).
+// one-launch BFGS + strong-Wolfe solve (dava_ba_solve_f64; dava_ba_solve_train_f64 with training mode's semantics).
 //
 // The reference trains and tests its calibration path in float64 (CalibrationNetwork under
 // float_precision="64"; tests/autograd_solvers, tests/geometry in float64).  This file runs the same
@@ -17,11 +17,17 @@
 // The recording form (dava_ba_solve_record_f64) is the same kernel behind a RECORD template flag: it
 // additionally writes dava_tape.hpp's layout in doubles (x_k, g_k at the start of every iteration, alpha_k,
 // rho_j, c_j, gamma) for the float64 adjoint (bfgs_adjoint_f64.hip); the tape's history block is its workspace.
-// Not here: dense / hybrid / global-vector modes, the drop path,
-// return_second_last, lean trials, no-move runs, on-chip history entries.
+// Training mode (dava_ba_solve_train_f64, dava_ba_solve_record_train_f64) is the same kernel behind a TRAIN
+// template flag, with bfgs_solve.hip's semantics: the drop path draws its stopping iteration once before the
+// loop (drop_uniform, the float32 generator and comparison: one schedule per seed in both precisions) and a
+// problem that leaves there reports DAVA_STOP_DROP; return_second_last moves x only after the step has passed
+// the minimum-step test.  The tape needs nothing more: the adjoint replays status[:, 0] steps.
+// Not here: dense / hybrid / global-vector modes, lean trials, no-move runs, on-chip history entries.
 #include "ba_objective.hpp"
 #include "dava_f64.hpp"
 #include "dava_tape.hpp"
+
+#include <type_traits>
 
 namespace dava {
 namespace f64 {
@@ -83,6 +89,13 @@ struct SolveArgs {
   int T;
 };
 
+// What the TRAIN instantiations take (the eval-mode ones keep SolveArgs, their kernel argument as it was)
+struct TrainArgs : SolveArgs {
+  float drop_p;  // training-mode drop path probability (0: none)
+  unsigned long long drop_seed;
+  int second_last;  // training mode's return_second_last: a minimum-step stop keeps x_k
+};
+
 template <bool GRAD, bool SLOPE, bool TRIAL, int RES>
 __device__ __forceinline__ void eval(const Layout& L, const double* x, const double* d, double alpha,
                                      const double* obs, const uint8_t* vis, double* grad, double* views,
@@ -91,8 +104,12 @@ __device__ __forceinline__ void eval(const Layout& L, const double* x, const dou
                                                                          scratch, buf, E, slope);
 }
 
-template <int RES, bool RECORD>
-__global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(SolveArgs a) {
+// TRAIN: training mode's drop path and return_second_last, as bfgs_solve.hip runs them in float32.  Everything
+// they add stands behind `if constexpr (TRAIN)` or folds away with `hold`: the eval-mode instantiations are the
+// code they were without the flag.
+template <int RES, bool RECORD, bool TRAIN>
+__global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(
+    std::conditional_t<TRAIN, TrainArgs, SolveArgs> a) {
   extern __shared__ __attribute__((aligned(16))) double lds64[];
   const Layout L = a.L;
   const int P = L.P, M = L.M, N = L.N, Pv = a.Pv;
@@ -139,7 +156,21 @@ __global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(SolveArgs 
   bool have_next = false;
   double E_next = 0.0;
 
-  for (int k = 0; k < a.iters; ++k) {
+  // Training mode: the drop path stops this problem at the top of iteration kend (a.iters: never), drawn once
+  // here with float32's generator and float comparison (drop_uniform, dava_common.hpp) and used as the loop's
+  // bound, so the loop itself carries nothing extra; return_second_last holds x back until the step has passed
+  // the minimum-step test.
+  int kend = a.iters;
+  bool hold = false;
+  if constexpr (TRAIN) {
+    if (a.drop_p > 0.f) {
+      kend = 0;
+      while (kend < a.iters && drop_uniform(a.drop_seed, (int)b, kend) > a.drop_p) ++kend;
+    }
+    hold = a.second_last != 0;
+  }
+  int k = 0;
+  for (; k < kend; ++k) {
     { double* t = g; g = gp; gp = t; }  // gp <- previous gradient; g <- the (trial) gradient buffer
     if (have_next) {
       E = E_next;
@@ -316,16 +347,31 @@ __global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(SolveArgs 
     // ---- take the step (bfgs_solver.py:191-199) and test its length (:203-207) ----
     {
       double r[1] = {0.0};
-      for (int i = tid; i < P; i += kBlock) {
-        const double si = fmul_rn(alpha, d[i]);
-        s[i] = si;
-        x[i] = fadd_rn(x[i], si);
-        r[0] += si * si;
+      if (hold) {  // x moves only once the step has passed the test (uniform branch; never in eval mode)
+        for (int i = tid; i < P; i += kBlock) {
+          const double si = fmul_rn(alpha, d[i]);
+          s[i] = si;
+          r[0] += si * si;
+        }
+      } else {
+        for (int i = tid; i < P; i += kBlock) {
+          const double si = fmul_rn(alpha, d[i]);
+          s[i] = si;
+          x[i] = fadd_rn(x[i], si);
+          r[0] += si * si;
+        }
       }
       block_sum<1>(r, scratch, buf); buf ^= 1;
-      ++steps;
+      ++steps;  // (the failed step counts: the status words equal the eval solve's)
       if (!(sqrt(r[0]) > a.min_step)) { reason = DAVA_STOP_STEP; break; }
+      if (hold) {  // the same additions, after the test (bfgs_solver.py:208-212)
+        for (int i = tid; i < P; i += kBlock) x[i] = fadd_rn(x[i], s[i]);
+        __syncthreads();
+      }
     }
+  }
+  if constexpr (TRAIN) {
+    if (k == kend && kend < a.iters) reason = DAVA_STOP_DROP;  // uniform
   }
 
   // ---- outputs ----
@@ -455,11 +501,14 @@ extern "C" size_t dava_ba_solve_workspace_bytes_f64(const DavaSceneF64* scene, c
   return f64::history_bytes(sc, config->iterations) + f64::kTailBytes;
 }
 
-// dava_ba_solve_f64 (tape == nullptr: `workspace` holds the history rows) and dava_ba_solve_record_f64
-// (`workspace` is the tape, whose first block is the history rows)
-static int solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0, double* x_out,
-                     double* error_out, int32_t* status_out, void* workspace, size_t workspace_bytes, bool record,
-                     void* stream) {
+// dava_ba_solve[_train]_f64 (record == false: `workspace` holds the history rows) and
+// dava_ba_solve_record[_train]_f64 (`workspace` is the tape, whose first block is the history rows).
+// training: null or all zero = eval mode, the instantiations without TRAIN.
+static int solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const DavaTrainingF64* training,
+                     const double* x0, double* x_out, double* error_out, int32_t* status_out, void* workspace,
+                     size_t workspace_bytes, bool record, void* stream) {
+  if (training && !(training->drop_path_p >= 0.f && training->drop_path_p <= 1.f)) return DAVA_ERR_INVALID_ARGUMENT;
+  const bool train = training && (training->drop_path_p > 0.f || training->return_second_last);
   DavaScene sc;
   const int st = f64::check_scene_f64(scene, true, sc);
   if (st != DAVA_OK) return st;
@@ -477,7 +526,7 @@ static int solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* confi
     // (the size the query reports, tail included: a queue counter put there later finds its bytes)
     return DAVA_ERR_WORKSPACE;
   }
-  f64::SolveArgs a;
+  f64::TrainArgs a;
   a.L = make_layout(&sc);
   a.B = sc.batch;
   a.Pv = round_up(sc.num_parameters, 4);
@@ -501,24 +550,45 @@ static int solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* confi
   a.tape_sc = record ? static_cast<double*>(workspace) + tl.scal : nullptr;
   a.tape_tail = record ? static_cast<double*>(workspace) + tl.vecs : nullptr;
   a.T = tl.T;
+  a.drop_p = train ? training->drop_path_p : 0.f;
+  a.drop_seed = train ? ((unsigned long long)training->drop_seed_hi << 32) | training->drop_seed_lo : 0ull;
+  a.second_last = train && training->return_second_last ? 1 : 0;
   const int lds = (int)f64::carve(sc.num_views, sc.num_points, a.Pv, a.kcap).total_bytes;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  auto go = [&](auto kernel) {
+  auto go = [&](auto kernel, const auto& args) {
     set_dynamic_lds(kernel, lds);
-    hipLaunchKernelGGL(kernel, dim3(a.B), dim3(kBlock), lds, s, a);
+    hipLaunchKernelGGL(kernel, dim3(a.B), dim3(kBlock), lds, s, args);
   };
+  const f64::SolveArgs& ev = a;  // the eval-mode kernels' argument
   const bool ray = sc.residual == DAVA_RESIDUAL_RAY_ANGLE;
-  if (ray && record) go(f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_RAY_ANGLE, true>);
-  else if (ray) go(f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_RAY_ANGLE, false>);
-  else if (record) go(f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_SQUARED_REPROJECTION, true>);
-  else go(f64::bfgs_ba_solve_f64_kernel<DAVA_RESIDUAL_SQUARED_REPROJECTION, false>);
+  constexpr int kRay = DAVA_RESIDUAL_RAY_ANGLE, kSq = DAVA_RESIDUAL_SQUARED_REPROJECTION;
+  if (train) {
+    if (ray && record) go(f64::bfgs_ba_solve_f64_kernel<kRay, true, true>, a);
+    else if (ray) go(f64::bfgs_ba_solve_f64_kernel<kRay, false, true>, a);
+    else if (record) go(f64::bfgs_ba_solve_f64_kernel<kSq, true, true>, a);
+    else go(f64::bfgs_ba_solve_f64_kernel<kSq, false, true>, a);
+  } else {
+    if (ray && record) go(f64::bfgs_ba_solve_f64_kernel<kRay, true, false>, ev);
+    else if (ray) go(f64::bfgs_ba_solve_f64_kernel<kRay, false, false>, ev);
+    else if (record) go(f64::bfgs_ba_solve_f64_kernel<kSq, true, false>, ev);
+    else go(f64::bfgs_ba_solve_f64_kernel<kSq, false, false>, ev);
+  }
   return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
 }
 
 extern "C" int dava_ba_solve_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0,
                                  double* x_out, double* error_out, int32_t* status_out, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  return solve_f64(scene, config, x0, x_out, error_out, status_out, workspace, workspace_bytes, false, stream);
+  return solve_f64(scene, config, nullptr, x0, x_out, error_out, status_out, workspace, workspace_bytes, false,
+                   stream);
+}
+
+extern "C" int dava_ba_solve_train_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                                       const DavaTrainingF64* training, const double* x0, double* x_out,
+                                       double* error_out, int32_t* status_out, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  return solve_f64(scene, config, training, x0, x_out, error_out, status_out, workspace, workspace_bytes, false,
+                   stream);
 }
 
 extern "C" size_t dava_ba_solve_tape_bytes_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config) {
@@ -531,7 +601,14 @@ extern "C" size_t dava_ba_solve_tape_bytes_f64(const DavaSceneF64* scene, const 
 extern "C" int dava_ba_solve_record_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const double* x0,
                                         double* x_out, double* error_out, int32_t* status_out, void* tape,
                                         size_t tape_bytes, void* stream) {
-  return solve_f64(scene, config, x0, x_out, error_out, status_out, tape, tape_bytes, true, stream);
+  return solve_f64(scene, config, nullptr, x0, x_out, error_out, status_out, tape, tape_bytes, true, stream);
+}
+
+extern "C" int dava_ba_solve_record_train_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                                              const DavaTrainingF64* training, const double* x0, double* x_out,
+                                              double* error_out, int32_t* status_out, void* tape, size_t tape_bytes,
+                                              void* stream) {
+  return solve_f64(scene, config, training, x0, x_out, error_out, status_out, tape, tape_bytes, true, stream);
 }
 
 extern "C" int dava_ba_evaluate_f64(const DavaSceneF64* scene, const double* x, const double* direction,

@@ -50,6 +50,19 @@ inline void set_dynamic_lds(Kernel kernel, int bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
+// Training mode's drop path (bfgs_solver.py:121-125): problem b keeps updating at iteration k iff
+// u(seed, b, k) > p, u uniform on [0, 1) with 24-bit resolution from a counter-based 64-bit mix
+// (splitmix64's finaliser over the packed counter): no state, any launch shape or work-queue
+// order draws the same schedule -- and the float32 and float64 solves the same one.
+__device__ __forceinline__ float drop_uniform(unsigned long long seed, int b, int k) {
+  unsigned long long z = seed ^ (((unsigned long long)(unsigned)b << 32) | (unsigned)k);
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (float)(z >> 40) * (1.0f / 16777216.0f);
+}
+
 // torch.clamp(min=lo) semantics: NaN propagates (fmaxf would swallow it).
 template <typename T>
 __device__ __forceinline__ T clamp_min(T v, T lo) { return v < lo ? lo : v; }

@@ -95,6 +95,16 @@ class DavaSolverConfigF64(ctypes.Structure):
     ]
 
 
+class DavaTrainingF64(ctypes.Structure):
+    """Training mode of the float64 fused solve (`dava_ba_solve_train_f64`, `dava_ba_solve_record_train_f64`)."""
+    _fields_ = [
+        ("drop_path_p", ctypes.c_float),
+        ("drop_seed_lo", ctypes.c_uint32),
+        ("drop_seed_hi", ctypes.c_uint32),
+        ("return_second_last", _c_i32),
+    ]
+
+
 class DavaSolvePlan(ctypes.Structure):
     _fields_ = [
         ("global_vectors", _c_i32),
@@ -128,6 +138,14 @@ SIGNATURES = {
     "dava_ba_solve_backward_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSolverConfigF64),
                                                   _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
                                                   _vp]),
+    # training mode of the float64 fused solve
+    "dava_ba_solve_train_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSolverConfigF64),
+                                               ctypes.POINTER(DavaTrainingF64), _vp, _vp, _vp, _vp, _vp,
+                                               ctypes.c_size_t, _vp]),
+    "dava_ba_solve_record_train_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64),
+                                                      ctypes.POINTER(DavaSolverConfigF64),
+                                                      ctypes.POINTER(DavaTrainingF64), _vp, _vp, _vp, _vp, _vp,
+                                                      ctypes.c_size_t, _vp]),
     "dava_ba_second_order": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 8),
     "dava_ba_second_order_obs": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 9),
     "dava_ba_solve_tape_bytes": (ctypes.c_size_t, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSolverConfig)]),

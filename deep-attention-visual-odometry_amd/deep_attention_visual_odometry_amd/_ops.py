@@ -61,6 +61,12 @@ def solver_config_f64(sufficient_decrease, curvature, error_threshold, iteration
                                  1 if strong else 0)
 
 
+def training_f64(drop_path_p: float = 0.0, drop_seed: int = 0, return_second_last: bool = False) -> N.DavaTrainingF64:
+    """Training mode of the float64 fused solve (all zero: eval mode, the eval launch)."""
+    seed = int(drop_seed) & 0xFFFFFFFFFFFFFFFF
+    return N.DavaTrainingF64(float(drop_path_p), seed & 0xFFFFFFFF, seed >> 32, 1 if return_second_last else 0)
+
+
 def solver_config(sufficient_decrease, curvature, error_threshold, iterations, minimum_step, max_line_search_trials,
                   strong, hessian_mode, drop_path_p: float = 0.0, drop_seed: int = 0,
                   return_second_last: bool = False) -> N.DavaSolverConfig:
@@ -109,15 +115,17 @@ def ba_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: in
     ``workspace``: a uint8 scratch buffer of at least ``dava_ba_solve_workspace_bytes`` (its contents
     are overwritten), or an empty tensor to allocate one per call.
     Returns (x, error (B,) or empty, status (B, 4) int32).
-    A float64 batch (parameters and observations) runs ``dava_ba_solve_f64``: compact history, eval mode."""
+    A float64 batch (parameters and observations) runs ``dava_ba_solve_train_f64``: compact history, the
+    training-mode arguments with the float32 semantics (all off: the launch of ``dava_ba_solve_f64``)."""
     lib = N.load_library()
     _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
     b = x0.shape[0]
     dev = x0.device
     if x0.dtype == torch.float64:
-        if hessian_mode != N.DAVA_HESSIAN_COMPACT or drop_path_p != 0.0 or return_second_last:
-            raise ValueError("the float64 fused solve runs the compact history in eval mode only "
-                             "(hessian_mode == DAVA_HESSIAN_COMPACT, drop_path_p == 0, no return_second_last)")
+        if hessian_mode != N.DAVA_HESSIAN_COMPACT:
+            raise ValueError("the float64 fused solve runs the compact history only "
+                             "(hessian_mode == DAVA_HESSIAN_COMPACT)")
+        train64 = training_f64(drop_path_p, drop_seed, return_second_last)
         sc64 = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
         cfg64 = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
                                   max_line_search_trials, strong)
@@ -134,9 +142,9 @@ def ba_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: in
         err = torch.empty(b, device=dev, dtype=torch.float64) if want_error else _empty0(x0)
         status = torch.empty((b, N.STATUS_WORDS), device=dev, dtype=torch.int32)
         with torch.cuda.device(dev):
-            N.check(lib.dava_ba_solve_f64(sc64, cfg64, N.ptr(x0), N.ptr(x_out), N.ptr(err) if want_error else None,
-                                          N.ptr(status), N.ptr(workspace), workspace.numel(), N.stream_of(dev)),
-                    "dava_ba_solve_f64")
+            N.check(lib.dava_ba_solve_train_f64(sc64, cfg64, train64, N.ptr(x0), N.ptr(x_out),
+                                                N.ptr(err) if want_error else None, N.ptr(status), N.ptr(workspace),
+                                                workspace.numel(), N.stream_of(dev)), "dava_ba_solve_train_f64")
         return x_out, err, status
     sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
     cfg = solver_config(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
@@ -419,9 +427,11 @@ def tape_bytes_f64(batch: int, p: int, iterations: int) -> int:
 def ba_solve_record_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
                         distortion: bool, sufficient_decrease: float, curvature: float, error_threshold: float,
                         iterations: int, minimum_step: float, max_line_search_trials: int, strong: bool,
-                        residual: int, want_error: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """``dava_ba_solve_record_f64``: the float64 fused solve (bitwise ``ba_solve``'s x, error and status on a
-    float64 batch) plus the float64 tape.  Returns (x, status (B, 4) int32, tape uint8, error (B,) or empty)."""
+                        residual: int, want_error: bool = False, drop_path_p: float = 0.0, drop_seed: int = 0,
+                        return_second_last: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``dava_ba_solve_record_train_f64``: the float64 fused solve (bitwise ``ba_solve``'s x, error and status on a
+    float64 batch, training-mode arguments included) plus the float64 tape.
+    Returns (x, status (B, 4) int32, tape uint8, error (B,) or empty)."""
     lib = N.load_library()
     _require_float64(x0, "the float64 recording solve")
     _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
@@ -429,6 +439,7 @@ def ba_solve_record_f64(x0: Tensor, observations: Tensor, visibility: Tensor, nu
     sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
     cfg = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
                             max_line_search_trials, strong)
+    train = training_f64(drop_path_p, drop_seed, return_second_last)
     need = int(lib.dava_ba_solve_tape_bytes_f64(sc, cfg))
     if need == 0:
         raise ValueError("this scene / configuration has no float64 fused solve (the LDS image must fit 160 KiB, "
@@ -440,15 +451,16 @@ def ba_solve_record_f64(x0: Tensor, observations: Tensor, visibility: Tensor, nu
     err = torch.empty(b, device=dev, dtype=torch.float64) if want_error else _empty0(x0)
     status = torch.empty((b, N.STATUS_WORDS), device=dev, dtype=torch.int32)
     with torch.cuda.device(dev):
-        N.check(lib.dava_ba_solve_record_f64(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(err) if want_error else None,
-                                             N.ptr(status), N.ptr(tape), tape.numel(), N.stream_of(dev)),
-                "dava_ba_solve_record_f64")
+        N.check(lib.dava_ba_solve_record_train_f64(sc, cfg, train, N.ptr(x0), N.ptr(x_out),
+                                                   N.ptr(err) if want_error else None, N.ptr(status), N.ptr(tape),
+                                                   tape.numel(), N.stream_of(dev)), "dava_ba_solve_record_train_f64")
     return x_out, status, tape, err
 
 
 @ba_solve_record_f64.register_fake
 def _(x0, observations, visibility, num_views, num_points, distortion, sufficient_decrease, curvature,
-      error_threshold, iterations, minimum_step, max_line_search_trials, strong, residual, want_error=False):
+      error_threshold, iterations, minimum_step, max_line_search_trials, strong, residual, want_error=False,
+      drop_path_p=0.0, drop_seed=0, return_second_last=False):
     b = x0.shape[0]
     return (torch.empty_like(x0), x0.new_empty((b, N.STATUS_WORDS), dtype=torch.int32),
             x0.new_empty((tape_bytes_f64(b, x0.shape[1], iterations),), dtype=torch.uint8),

@@ -25,12 +25,15 @@ double backward is the forward-over-reverse kernel (H v and the observation
 cross term, csrc/ba_second_order.hip), so gradients reach captured observations.
 
 float64: an objective built from float64 device observations also solves float64 parameters in one launch
-(``dava_ba_solve_f64``: compact history, eval-mode semantics, no graph); what that kernel does not cover
-(dense mode, more than 1025 iterations, training mode's drop path) runs the generic loop with the float64
-objective as its closure.  float64 parameters that require grad raise ``TypeError`` unless the objective was
-built with ``float64_derivatives=True``: then the solve is differentiated by the recording float64 solve and
-its adjoint kernel (``dava_ba_solve_record_f64`` / ``dava_ba_solve_backward_f64``), or by the generic loop
-with torch's graph where those do not apply (dense mode, the GENERIC_BACKWARD override, training mode).
+(``dava_ba_solve_f64``: compact history, no graph); what that kernel does not cover (dense mode, more than
+1025 iterations) runs the generic loop with the float64 objective as its closure.  float64 parameters that
+require grad raise ``TypeError`` unless the objective was built with ``float64_derivatives=True``: then the
+solve is differentiated by the recording float64 solve and its adjoint kernel (``dava_ba_solve_record_f64`` /
+``dava_ba_solve_backward_f64``), or by the generic loop with torch's graph where those do not apply (dense
+mode, the GENERIC_BACKWARD override).  The same keyword is the opt-in for float64 training mode: with it the
+drop path and ``return_second_last`` run fused under the float32 rules below (``dava_ba_solve_train_f64``,
+``dava_ba_solve_record_train_f64``); without it a training-mode float64 call runs the generic loop with
+torch's random stream, as before.
 
 Training mode's ``return_second_last`` runs fused too (a problem stopped by the minimum-step rule
 keeps x before its last step); when the reference's scatter would have moved rows between problems
@@ -236,12 +239,16 @@ class BFGSSolver(Module):
 
     def _forward_f64(self, parameters, fn: ReprojectionError, error_threshold, num_iterations, drop_p, second_last):
         """float64 parameters on an objective built from float64 device observations: one launch of
-        ``dava_ba_solve_f64`` (compact history, eval-mode semantics) where it applies, else the generic loop
+        ``dava_ba_solve_f64`` (compact history) where it applies, else the generic loop
         with the objective as its closure (its float64 value and first derivative are HIP kernels too).
         Differentiating through a float64 solve needs an objective built with ``float64_derivatives=True``
         (without it: ``TypeError``, second derivatives are float32 only): the recording float64 solve and its
         adjoint kernel (``dava_ba_solve_record_f64`` / ``dava_ba_solve_backward_f64``) where they apply and the
-        GENERIC_BACKWARD override is off, else the generic loop with the graph kept by torch."""
+        GENERIC_BACKWARD override is off, else the generic loop with the graph kept by torch.
+        Training mode (a drop path, ``return_second_last``) takes the same fused routes when the objective was
+        built with that keyword and the GENERIC_TRAINING override is off: the seed of the counter-based schedule
+        comes from torch's default generator, and a ``return_second_last`` batch in which the reference's scatter
+        would have moved rows is redone by the generic loop, as in float32."""
         if parameters.requires_grad and not fn.float64_derivatives:
             raise TypeError("differentiating through a float64 solve needs second derivatives of the fused "
                             "objectives, which are float32 only")
@@ -249,7 +256,12 @@ class BFGSSolver(Module):
         if fn.batch_shape != lead:
             raise ValueError(f"ReprojectionError batch shape {tuple(fn.batch_shape)} != parameters {tuple(lead)}")
         x0 = parameters.reshape(-1, parameters.size(-1))
-        fused = (drop_p == 0.0 and not second_last and self.hessian_mode != "dense"
+        # training mode runs fused only on an objective built with float64_derivatives=True (the float64 training
+        # opt-in), and its drop path not under the GENERIC_TRAINING override
+        training = drop_p > 0.0 or second_last
+        fused = ((not training or (fn.float64_derivatives
+                                   and not (drop_p > 0.0 and _native.python_knob("GENERIC_TRAINING"))))
+                 and self.hessian_mode != "dense"
                  and 1 <= num_iterations <= self.MAX_COMPACT_ENTRIES + 1
                  and native_ops.solve_workspace_bytes_f64(max(x0.shape[0], 1), fn.num_views, fn.num_points,
                                                           fn.distortion, num_iterations, fn.residual) > 0)
@@ -257,27 +269,24 @@ class BFGSSolver(Module):
             fused = (fused and not _native.python_knob("GENERIC_BACKWARD")
                      and native_ops.solve_tape_supported_f64(max(x0.shape[0], 1), fn.num_views, fn.num_points,
                                                              fn.distortion, num_iterations, fn.residual))
-            if fused:
-                x, status = native_ops.ba_solve_differentiable_f64(
-                    x0, fn.observations64.reshape(-1, fn.num_views, fn.num_points, 2),
-                    fn.visibility.reshape(-1, fn.num_views, fn.num_points), fn.num_views, fn.num_points,
-                    fn.distortion, sufficient_decrease=self.sufficient_decrease, curvature=self.curvature,
-                    error_threshold=error_threshold, iterations=num_iterations, minimum_step=self.minimum_step,
-                    residual=fn.residual)
+        if fused:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0.0 else 0  # from torch's default generator
+            scene = (x0, fn.observations64.reshape(-1, fn.num_views, fn.num_points, 2),
+                     fn.visibility.reshape(-1, fn.num_views, fn.num_points), fn.num_views, fn.num_points, fn.distortion)
+            kw = dict(sufficient_decrease=self.sufficient_decrease, curvature=self.curvature,
+                      error_threshold=error_threshold, iterations=num_iterations, minimum_step=self.minimum_step,
+                      residual=fn.residual, drop_path_p=drop_p, drop_seed=seed, return_second_last=second_last)
+            if parameters.requires_grad:
+                x, status = native_ops.ba_solve_differentiable_f64(*scene, **kw)
+            else:
+                x, _, status = native_ops.ba_solve(*scene, hessian_mode=_native.DAVA_HESSIAN_COMPACT,
+                                                   want_status=True, **kw)
+            if not (second_last and native_ops.second_last_moves_rows(status)):
                 self.last_status = status
                 return x.reshape(parameters.shape)
-        if not fused:
-            self.last_status = None  # the generic loop has no status words
-            self._check_generic_fits(parameters, num_iterations, second_last)
-            return self._generic(parameters, fn, error_threshold, num_iterations)
-        x, _, status = native_ops.ba_solve(
-            x0, fn.observations64.reshape(-1, fn.num_views, fn.num_points, 2),
-            fn.visibility.reshape(-1, fn.num_views, fn.num_points), fn.num_views, fn.num_points, fn.distortion,
-            sufficient_decrease=self.sufficient_decrease, curvature=self.curvature, error_threshold=error_threshold,
-            iterations=num_iterations, minimum_step=self.minimum_step, hessian_mode=_native.DAVA_HESSIAN_COMPACT,
-            want_status=True, residual=fn.residual)
-        self.last_status = status
-        return x.reshape(parameters.shape)
+        self.last_status = None  # the generic loop has no status words
+        self._check_generic_fits(parameters, num_iterations, second_last)
+        return self._generic(parameters, fn, error_threshold, num_iterations)
 
     MAX_COMPACT_ENTRIES = 1024  # kMaxCompactEntries in csrc/solve_plan.hpp
 

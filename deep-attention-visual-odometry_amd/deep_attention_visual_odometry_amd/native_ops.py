@@ -117,8 +117,8 @@ def ba_solve(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Ten
     ``drop_path_p`` > 0: training mode's drop path with the counter-based schedule of ``drop_seed``.
     ``return_second_last``: a problem stopped by the minimum-step rule returns x before its last step
     (see :func:`second_last_moves_rows` for the one case the reference does differently).
-    float64 parameters with float64 observations run the float64 solve: ``hessian_mode`` must be
-    ``DAVA_HESSIAN_COMPACT``, ``drop_path_p`` 0 and ``return_second_last`` off."""
+    float64 parameters with float64 observations run the float64 solve (``hessian_mode`` must be
+    ``DAVA_HESSIAN_COMPACT``); a ``drop_seed`` draws the same schedule there as in float32."""
     x0 = _float_on_device(x0, "parameters")
     obs, vis = _scene_inputs(x0, observations, visibility)
     x, err, status = torch.ops.dava.ba_solve(
@@ -232,17 +232,23 @@ def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distor
 
 class _FusedSolveF64(torch.autograd.Function):
     """:class:`_FusedSolve` in float64: the recording float64 solve (``dava_ba_solve_record_f64``) and its adjoint
-    kernel (csrc/bfgs_adjoint_f64.hip).  Eval-mode semantics only.  Not differentiable twice."""
+    kernel (csrc/bfgs_adjoint_f64.hip), training mode's drop path and return_second_last included.  Not
+    differentiable twice."""
 
     @staticmethod
     def forward(ctx, x0, observations, visibility, num_views, num_points, distortion, residual, cfg):
-        c1, c2, thr, iters, min_step, trials, strong = cfg
+        c1, c2, thr, iters, min_step, trials, strong, drop_p, drop_seed, second_last = cfg
         x0c = _f64_on_device(x0, "parameters")
         obs, vis = _scene_inputs(x0c, observations, visibility)
         x, status, tape, _ = torch.ops.dava.ba_solve_record_f64(
             x0c, obs, vis, int(num_views), int(num_points), bool(distortion), float(c1), float(c2), float(thr),
-            int(iters), float(min_step), int(trials), bool(strong), int(residual), False)
-        ctx.save_for_backward(tape, status, obs, vis)
+            int(iters), float(min_step), int(trials), bool(strong), int(residual), False, float(drop_p),
+            int(drop_seed), bool(second_last))
+        replay = status
+        if second_last:  # a minimum-step stop returned x before its last step: the adjoint replays one fewer
+            replay = status.clone()
+            replay[:, 0] -= (status[:, 1] == N.STOP_STEP).to(torch.int32)
+        ctx.save_for_backward(tape, replay, obs, vis)
         ctx.meta = (int(num_views), int(num_points), bool(distortion), int(iters), int(residual))
         ctx.mark_non_differentiable(status)
         ctx.recorded = torch.cuda.Event()  # the tape is complete once the recording launch is
@@ -270,10 +276,13 @@ def ba_solve_differentiable_f64(x0: torch.Tensor, observations: torch.Tensor, vi
                                 sufficient_decrease: float = 1e-4, curvature: float = 0.9,
                                 error_threshold: float = 1e-4, iterations: int = 1000, minimum_step: float = 1e-8,
                                 max_line_search_trials: int = 1000, strong: bool = True,
-                                residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION):
-    """The float64 fused solve as an autograd node w.r.t. x0 and the (float64) observations.
+                                residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, drop_path_p: float = 0.0,
+                                drop_seed: int = 0, return_second_last: bool = False):
+    """The float64 fused solve as an autograd node w.r.t. x0 and the (float64) observations, in eval mode or
+    with training mode's drop path / return_second_last (as :func:`ba_solve_differentiable`).
     Returns (x, status)."""
-    cfg = (sufficient_decrease, curvature, error_threshold, iterations, minimum_step, max_line_search_trials, strong)
+    cfg = (sufficient_decrease, curvature, error_threshold, iterations, minimum_step, max_line_search_trials, strong,
+           drop_path_p, drop_seed, return_second_last)
     return _FusedSolveF64.apply(x0, observations, visibility, num_views, num_points, distortion, residual, cfg)
 
 

@@ -199,10 +199,11 @@ int dava_ba_evaluate(const DavaScene* scene, const float* x, const float* direct
 
 /* ---- float64 flavour of the evaluation and of the fused solve (additive to ABI 4) ----
  * The same objectives and the same algorithm with every value a double: parameters, observations,
- * thresholds (1e-4 as a double is the reference's 1e-4), history rows.  COMPACT inverse Hessian only,
- * eval mode only (no drop path, no return_second_last; the tape: dava_ba_solve_record_f64 below), one
- * 256-thread workgroup per problem with its whole state in LDS: a shape is supported when that image
- * fits 160 KiB (C1-C3 do; C5 does not) and 1 <= iterations <= 1025.  Anything else:
+ * thresholds (1e-4 as a double is the reference's 1e-4), history rows.  COMPACT inverse Hessian only;
+ * dava_ba_solve_f64 / dava_ba_solve_record_f64 run eval mode, training mode's drop path and
+ * return_second_last go through dava_ba_solve_train_f64 / dava_ba_solve_record_train_f64 (DavaTrainingF64,
+ * below).  One 256-thread workgroup per problem with its whole state in LDS: a shape is supported when
+ * that image fits 160 KiB (C1-C3 do; C5 does not) and 1 <= iterations <= 1025.  Anything else:
  * DAVA_ERR_UNSUPPORTED, and 0 from the size query. */
 typedef struct DavaSceneF64 {
   int32_t batch;               /* B >= 0                               */
@@ -274,6 +275,38 @@ size_t dava_ba_solve_backward_workspace_bytes_f64(const DavaSceneF64* scene, con
 int dava_ba_solve_backward_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const void* tape,
                                size_t tape_bytes, const int32_t* status, const double* x_out_grad, double* x0_grad,
                                double* observations_grad, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- training mode of the float64 fused solve (additive to ABI 4) ----
+ * DavaSolverConfig's training fields for the float64 entry points, with the float32 solve's semantics:
+ *   drop_path_p > 0     before its first iteration a problem draws the iteration at which the drop path
+ *                       stops it (bfgs_solver.py:121-125) from the counter-based generator of
+ *                       (drop_seed, problem, iteration); the draw and its comparison with drop_path_p
+ *                       are the float32 solve's, so one seed gives one schedule in both precisions.
+ *                       A problem stopped this way reports DAVA_STOP_DROP; one stopped at iteration 0
+ *                       returns x0 with 0 steps.
+ *   return_second_last  a problem stopped by the minimum-step rule returns x before its last step
+ *                       (bfgs_solver.py:196-212).  Its status words are the eval solve's: steps counts
+ *                       the failed step.  A caller that differentiates such a solve therefore hands
+ *                       dava_ba_solve_backward_f64 (as dava_ba_solve_backward in float32) a status whose
+ *                       step count is one lower for every problem that stopped with DAVA_STOP_STEP: the
+ *                       adjoint replays status[b][0] steps.
+ * training == NULL, or a struct whose fields are all zero, is eval mode: the very launch of
+ * dava_ba_solve_f64 / dava_ba_solve_record_f64.  drop_path_p outside [0, 1] (or NaN):
+ * DAVA_ERR_INVALID_ARGUMENT, checked on the host before anything else.  Neither size query depends on
+ * the training fields, and dava_ba_solve_backward_f64 takes tapes of either mode. */
+typedef struct DavaTrainingF64 {
+  float drop_path_p;                    /* [0, 1]; 0 = eval mode */
+  uint32_t drop_seed_lo, drop_seed_hi;
+  int32_t return_second_last;
+} DavaTrainingF64;
+
+int dava_ba_solve_train_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                            const DavaTrainingF64* training, const double* x0, double* x_out, double* error_out,
+                            int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream);
+int dava_ba_solve_record_train_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                                   const DavaTrainingF64* training, const double* x0, double* x_out,
+                                   double* error_out, int32_t* status_out, void* tape, size_t tape_bytes,
+                                   void* stream);
 
 /* Second derivatives of the objective, for differentiating THROUGH a solve whose error
  * function is a fused objective (the reference's create_graph double backward,

@@ -14,6 +14,14 @@ generic float64 loop, one JSON line per configuration (default: profiles/f64_sol
                  float64 fused route against the generic float64 loop with torch's graph (GENERIC_BACKWARD).
   No rate is a requirement in this mode: the numbers are reported as measured.
 
+--mode train (default output profiles/f64_training.jsonl): training mode as the reference trains (drop_path_p = 0.1),
+solve PLUS gradient through the drop-in on an objective built with float64_derivatives=True:
+  c3_b32_k20, c2_b1024_k100   the fused route (dava_ba_solve_record_train_f64 + the adjoint, counter-based drop
+                 schedule) against the generic float64 loop with torch's graph and torch's random stream
+                 (GENERIC_TRAINING), alternated run by run in one process.  The two draw different schedules from
+                 the same distribution; the mean steps per problem of the fused runs is reported.
+  No rate is a requirement in this mode either.
+
 Timing: device events around each solve, every shape warmed up first, median of --repeats (>= 5) solves.
 Reported: problems/s, algorithmic HBM bytes (bench.py's compact model; 8-byte elements for float64, computed
 here), the fraction of 8 TB/s they amount to, and the ratio to the fp32 fused rate.  The one requirement
@@ -206,27 +214,81 @@ def grad_vs_generic(tag, b, m, n, distortion, k, repeats, dev):
             "max_rel_difference_fused_vs_generic": {"x0_grad": rel[0], "observations_grad": rel[1]}}
 
 
+def train_vs_generic(tag, b, m, n, distortion, k, repeats, dev, drop_p=0.1):
+    """Training mode (drop path) solve + backward in float64 through the drop-in: the fused route against the generic
+    loop with torch's graph, alternated run by run."""
+    from deep_attention_visual_odometry_amd import BFGSSolver, ReprojectionError, _native
+
+    x32, obs32, vis = scene(b, m, n, distortion, dev)
+    x64, obs64 = x32.double(), obs32.double()
+    w = torch.randn(x64.shape, generator=torch.Generator().manual_seed(1), dtype=torch.float64).to(dev)
+    solver = BFGSSolver(drop_path_p=drop_p, training_iterations=k, training_error_threshold=-1.0, minimum_step=-1.0)
+    assert solver.training
+    steps = []
+
+    def run(name):
+        xg, og = x64.clone().requires_grad_(True), obs64.clone().requires_grad_(True)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        with _native.debug_overrides(GENERIC_TRAINING=1 if name == "generic" else -1):
+            out = solver(xg, ReprojectionError(og, vis, m, n, distortion, float64_derivatives=True))
+        gx, go = torch.autograd.grad((out * w).sum(), [xg, og])
+        end.record()
+        end.synchronize()
+        assert (solver.last_status is not None) == (name == "fused")
+        assert torch.isfinite(gx).all() and torch.isfinite(go).all()
+        if name == "fused":
+            steps.append(solver.last_status[:, 0].float().mean().item())
+        return start.elapsed_time(end) * 1e-3
+
+    torch.manual_seed(0)
+    for name in ("fused", "generic"):  # warm-up of both (module load, allocator)
+        run(name)
+    times = {"fused": [], "generic": []}
+    for _ in range(repeats):
+        for name in times:
+            times[name].append(run(name))
+    fused, generic = statistics.median(times["fused"]), statistics.median(times["generic"])
+    return {"config": "train_" + tag, "batch": b, "views": m, "points": n, "distortion": distortion, "iterations": k,
+            "drop_path_p": drop_p, "repeats": repeats, "device": torch.cuda.get_device_name(dev),
+            "f64_fused": {"median_s": fused, "min_s": min(times["fused"]), "problems_per_s": b / fused,
+                          "mean_steps_per_problem": statistics.mean(steps[1:])},
+            "f64_generic_graph": {"median_s": generic, "min_s": min(times["generic"]), "problems_per_s": b / generic},
+            "fused_over_generic_rate": generic / fused}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--mode", choices=("solve", "grad"), default="solve",
-                    help="solve: the solve alone (the default); grad: solve plus gradient")
+    ap.add_argument("--mode", choices=("solve", "grad", "train"), default="solve",
+                    help="solve: the solve alone (the default); grad: solve plus gradient; train: training mode's "
+                         "drop path, solve plus gradient")
     ap.add_argument("--out", default=None,
-                    help="default: profiles/f64_solve.jsonl (solve), profiles/f64_adjoint.jsonl (grad)")
+                    help="default: profiles/f64_solve.jsonl (solve), profiles/f64_adjoint.jsonl (grad), "
+                         "profiles/f64_training.jsonl (train)")
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--configs", default=None, help="default: c2,c3,c3_b256_k20 (solve), c2,c3,c3_b32_k20 (grad)")
+    ap.add_argument("--configs", default=None, help="default: c2,c3,c3_b256_k20 (solve), c2,c3,c3_b32_k20 (grad), "
+                                                     "c3_b32_k20,c2_b1024_k100 (train)")
     args = ap.parse_args(argv)
-    grad = args.mode == "grad"
+    grad, train = args.mode == "grad", args.mode == "train"
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "f64_adjoint.jsonl" if grad else "f64_solve.jsonl")
+        args.out = os.path.join(REPO, "profiles", {"solve": "f64_solve.jsonl", "grad": "f64_adjoint.jsonl",
+                                                   "train": "f64_training.jsonl"}[args.mode])
     if args.configs is None:
-        args.configs = "c2,c3,c3_b32_k20" if grad else "c2,c3,c3_b256_k20"
+        args.configs = {"solve": "c2,c3,c3_b256_k20", "grad": "c2,c3,c3_b32_k20",
+                        "train": "c3_b32_k20,c2_b1024_k100"}[args.mode]
     if args.repeats < 5:
         ap.error("--repeats must be at least 5 (the median of at least 5 timed solves)")
     assert torch.cuda.is_available(), "measure_f64.py needs a ROCm device"
     dev = torch.device("cuda", 0)
     lines, ok = [], True
     for name in args.configs.split(","):
-        if grad and name == "c2":
+        if train and name == "c3_b32_k20":
+            lines.append(train_vs_generic(name, 32, 4, 256, True, 20, args.repeats, dev))
+        elif train and name == "c2_b1024_k100":
+            lines.append(train_vs_generic(name, 1024, 2, 128, False, 100, args.repeats, dev))
+        elif train:
+            ap.error(f"unknown configuration {name!r} for --mode train")
+        elif grad and name == "c2":
             lines.append(grad_pair("c2", 1024, 2, 128, False, 100, args.repeats, dev))
         elif grad and name == "c3":
             lines.append(grad_pair("c3", 8192, 4, 256, True, 100, args.repeats, dev))
