@@ -26,6 +26,7 @@ enum DebugKnob : int {
   kDbgCompactSwitch,  // >= 1: COMPACT history capacity before the dense fold (default 1024; tests)
   kDbgGvScalarSlice,  // 0 | 1: GV wide pass's rho_j, c_j in LDS / in the workspace slice (default: by fit)
   kDbgAdjScGlobal,    // 0 | 1: LDS-mode adjoint's tape scalar row staged in LDS / read in place (default: by fit)
+  kDbgF64Form,        // 1 | 2: raises the float64 kernels' form (solve_f64.hpp) above the one the fit chooses
   kDbgKnobs
 };
 

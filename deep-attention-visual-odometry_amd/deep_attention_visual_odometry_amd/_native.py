@@ -27,14 +27,16 @@ LIB_PATH = (_DEBUG_ENV and os.environ.get("DAVA_LIB")) or os.path.join(_HERE, "_
 # Overridable launch choices of the library (csrc/dava_debug.hpp), and of this package's Python side
 LIBRARY_KNOBS = ("FORCE_GV", "GV_NO_XL", "SOLVE_WAVES", "WG_PER_CU", "LDS_HISTORY", "STAGGER", "STAGGER_LEVELS",
                  "NO_PPT", "NO_QUEUE", "ADJ_GV_WAVES", "ADJ_FORCE_GV", "ADJ_LDS_ENTRIES", "ADJ_GD_HBM",
-                 "COMPACT_SWITCH", "GV_SCALAR_SLICE", "ADJ_SC_GLOBAL")
+                 "COMPACT_SWITCH", "GV_SCALAR_SLICE", "ADJ_SC_GLOBAL", "F64_FORM")
 # GENERIC_BACKWARD: differentiate a fused objective's solve with the generic loop, not the adjoint;
 # GENERIC_TRAINING: training mode's drop path with the generic loop and torch's own RNG;
 # GENERIC_DENSE: the generic loop keeps the reference's dense (B, P, P) inverse Hessian even without a graph
 PYTHON_KNOBS = ("GENERIC_BACKWARD", "GENERIC_TRAINING", "GENERIC_DENSE")
 _py_knobs = {k: -1 for k in PYTHON_KNOBS}
+_lib_knobs = {}  # the library overrides set through this module (name -> value >= 0), for routing that follows one
 
 DAVA_OK = 0
+DAVA_ERR_UNSUPPORTED = 4
 DAVA_HESSIAN_DENSE = 0
 DAVA_HESSIAN_COMPACT = 1
 DAVA_RESIDUAL_SQUARED_REPROJECTION = 0
@@ -146,6 +148,14 @@ SIGNATURES = {
                                                       ctypes.POINTER(DavaSolverConfigF64),
                                                       ctypes.POINTER(DavaTrainingF64), _vp, _vp, _vp, _vp, _vp,
                                                       ctypes.c_size_t, _vp]),
+    # float64 evaluation and solve beyond the LDS image (forms 1 and 2, csrc/bfgs_solve_large_f64.hip)
+    "dava_ba_solve_form_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_large_workspace_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                                  ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_large_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSolverConfigF64),
+                                               ctypes.POINTER(DavaTrainingF64), _vp, _vp, _vp, _vp, _vp,
+                                               ctypes.c_size_t, _vp]),
+    "dava_ba_evaluate_large_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dava_ba_second_order": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 8),
     "dava_ba_second_order_obs": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 9),
     "dava_ba_solve_tape_bytes": (ctypes.c_size_t, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSolverConfig)]),
@@ -233,10 +243,23 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                     _py_knobs[k] = v
                 elif hasattr(lib, "dava_debug_set_override"):
                     lib.dava_debug_set_override(k.encode(), v)
+                    _note_library_knob(k, v)
         return lib
 
 
 _DEFAULT_LIB = os.path.join(_HERE, "_lib", "libdava_ba.so")
+
+
+def _note_library_knob(name: str, value: int) -> None:
+    if value >= 0:
+        _lib_knobs[name] = int(value)
+    else:
+        _lib_knobs.pop(name, None)
+
+
+def library_knob(name: str) -> int:
+    """The library override `name` (LIBRARY_KNOBS) as set through this module, or -1 when it is not set."""
+    return _lib_knobs.get(name, -1)
 
 
 def set_debug_override(name: str, value: int) -> None:
@@ -249,6 +272,7 @@ def set_debug_override(name: str, value: int) -> None:
     lib = load_library()
     if hasattr(lib, "dava_debug_set_override"):
         check(lib.dava_debug_set_override(name.encode(), int(value)), "dava_debug_set_override")
+        _note_library_knob(name, int(value))
 
 
 def clear_debug_overrides() -> None:
@@ -257,6 +281,7 @@ def clear_debug_overrides() -> None:
     lib = load_library()
     if hasattr(lib, "dava_debug_clear_overrides"):
         lib.dava_debug_clear_overrides()
+        _lib_knobs.clear()
 
 
 def python_knob(name: str) -> bool:

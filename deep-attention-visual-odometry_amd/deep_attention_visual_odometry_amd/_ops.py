@@ -116,7 +116,8 @@ def ba_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: in
     are overwritten), or an empty tensor to allocate one per call.
     Returns (x, error (B,) or empty, status (B, 4) int32).
     A float64 batch (parameters and observations) runs ``dava_ba_solve_train_f64``: compact history, the
-    training-mode arguments with the float32 semantics (all off: the launch of ``dava_ba_solve_f64``)."""
+    training-mode arguments with the float32 semantics (all off: the launch of ``dava_ba_solve_f64``) -- or, for a
+    scene beyond that kernel's LDS image, ``dava_ba_solve_large_f64`` with the same contract."""
     lib = N.load_library()
     _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
     b = x0.shape[0]
@@ -129,10 +130,15 @@ def ba_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: in
         sc64 = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
         cfg64 = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
                                   max_line_search_trials, strong)
+        # the symbols of the LDS image where it fits (and no F64_FORM override asks for another form), else the
+        # ones that take any scene size (forms 1 and 2: the scene, then the vectors too, out of LDS)
         need = int(lib.dava_ba_solve_workspace_bytes_f64(sc64, cfg64))
+        large = need == 0 or N.library_knob("F64_FORM") > 0
+        if large:
+            need = int(lib.dava_ba_solve_large_workspace_bytes_f64(sc64, cfg64))
         if need == 0:
-            raise ValueError("this scene / configuration has no float64 fused solve (the LDS image must fit "
-                             "160 KiB, 1 <= iterations <= 1025)")
+            raise ValueError("this scene / configuration has no float64 fused solve (1 <= iterations <= 1025, "
+                             "at most 251 views at 1025 iterations)")
         if workspace.numel() < need or workspace.device != dev or workspace.dtype != torch.uint8:
             if workspace.numel() > 0:
                 raise ValueError(f"workspace holds {workspace.numel()} bytes, the solve needs {need} "
@@ -141,10 +147,11 @@ def ba_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: in
         x_out = torch.empty_like(x0)
         err = torch.empty(b, device=dev, dtype=torch.float64) if want_error else _empty0(x0)
         status = torch.empty((b, N.STATUS_WORDS), device=dev, dtype=torch.int32)
+        name = "dava_ba_solve_large_f64" if large else "dava_ba_solve_train_f64"
         with torch.cuda.device(dev):
-            N.check(lib.dava_ba_solve_train_f64(sc64, cfg64, train64, N.ptr(x0), N.ptr(x_out),
-                                                N.ptr(err) if want_error else None, N.ptr(status), N.ptr(workspace),
-                                                workspace.numel(), N.stream_of(dev)), "dava_ba_solve_train_f64")
+            N.check(getattr(lib, name)(sc64, cfg64, train64, N.ptr(x0), N.ptr(x_out),
+                                       N.ptr(err) if want_error else None, N.ptr(status), N.ptr(workspace),
+                                       workspace.numel(), N.stream_of(dev)), name)
         return x_out, err, status
     sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
     cfg = solver_config(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
@@ -216,11 +223,16 @@ def ba_evaluate(x: Tensor, observations: Tensor, visibility: Tensor, num_views: 
     slope = torch.empty(b, device=x.device, dtype=x.dtype) if want_slope else _empty0(x)
     if x.dtype == torch.float64:
         sc64 = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+        args = (sc64, N.ptr(x), N.ptr(direction), N.ptr(alpha), N.ptr(err), N.ptr(grad) if want_grad else None,
+                N.ptr(slope) if want_slope else None, N.stream_of(x.device))
         with torch.cuda.device(x.device):
-            N.check(lib.dava_ba_evaluate_f64(sc64, N.ptr(x), N.ptr(direction), N.ptr(alpha), N.ptr(err),
-                                             N.ptr(grad) if want_grad else None,
-                                             N.ptr(slope) if want_slope else None, N.stream_of(x.device)),
-                    "dava_ba_evaluate_f64")
+            # the LDS image where it fits (refused on the host, before any launch, where it does not), else --
+            # or under the F64_FORM override -- the evaluation that takes any scene size
+            st = N.DAVA_ERR_UNSUPPORTED if N.library_knob("F64_FORM") > 0 else lib.dava_ba_evaluate_f64(*args)
+            if st == N.DAVA_ERR_UNSUPPORTED:
+                N.check(lib.dava_ba_evaluate_large_f64(*args), "dava_ba_evaluate_large_f64")
+            else:
+                N.check(st, "dava_ba_evaluate_f64")
         return err, grad, slope
     sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
     with torch.cuda.device(x.device):

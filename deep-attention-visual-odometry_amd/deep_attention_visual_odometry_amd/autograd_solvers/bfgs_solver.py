@@ -239,7 +239,8 @@ class BFGSSolver(Module):
 
     def _forward_f64(self, parameters, fn: ReprojectionError, error_threshold, num_iterations, drop_p, second_last):
         """float64 parameters on an objective built from float64 device observations: one launch of
-        ``dava_ba_solve_f64`` (compact history) where it applies, else the generic loop
+        ``dava_ba_solve_f64`` -- ``dava_ba_solve_large_f64`` for a scene beyond its LDS image -- (compact history)
+        where it applies, else the generic loop
         with the objective as its closure (its float64 value and first derivative are HIP kernels too).
         Differentiating through a float64 solve needs an objective built with ``float64_derivatives=True``
         (without it: ``TypeError``, second derivatives are float32 only): the recording float64 solve and its
@@ -259,12 +260,22 @@ class BFGSSolver(Module):
         # training mode runs fused only on an objective built with float64_derivatives=True (the float64 training
         # opt-in), and its drop path not under the GENERIC_TRAINING override
         training = drop_p > 0.0 or second_last
+        shape = (max(x0.shape[0], 1), fn.num_views, fn.num_points, fn.distortion, num_iterations, fn.residual)
         fused = ((not training or (fn.float64_derivatives
                                    and not (drop_p > 0.0 and _native.python_knob("GENERIC_TRAINING"))))
                  and self.hessian_mode != "dense"
                  and 1 <= num_iterations <= self.MAX_COMPACT_ENTRIES + 1
-                 and native_ops.solve_workspace_bytes_f64(max(x0.shape[0], 1), fn.num_views, fn.num_points,
-                                                          fn.distortion, num_iterations, fn.residual) > 0)
+                 and (native_ops.solve_workspace_bytes_f64(*shape) > 0
+                      or native_ops.solve_large_workspace_bytes_f64(*shape) > 0))
+        one = shape[:4] + (1, fn.residual)  # (the scene alone decides: the smallest image, one iteration)
+        if (parameters.requires_grad and native_ops.solve_workspace_bytes_f64(*one) == 0
+                and native_ops.solve_large_workspace_bytes_f64(*one) > 0):
+            # beyond the LDS image there is no recording solve, no adjoint and no second derivative of the
+            # objective, so the generic loop's graph could not be built either: refused here, before any launch
+            raise ValueError(
+                f"differentiating through a float64 solve of {fn.num_views} views x {fn.num_points} points: the "
+                "recording solve, its adjoint and the float64 second derivatives keep one problem's whole image in "
+                "LDS, which must fit 160 KiB; this scene solves and evaluates in float64 without a graph only")
         if parameters.requires_grad:  # the solve is a graph node only when the parameters require grad
             fused = (fused and not _native.python_knob("GENERIC_BACKWARD")
                      and native_ops.solve_tape_supported_f64(max(x0.shape[0], 1), fn.num_views, fn.num_points,

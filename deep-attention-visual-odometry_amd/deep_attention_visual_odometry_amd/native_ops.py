@@ -304,6 +304,30 @@ def solve_workspace_bytes_f64(batch: int, num_views: int, num_points: int, disto
     return int(N.load_library().dava_ba_solve_workspace_bytes_f64(sc, cfg))
 
 
+def solve_form_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1000,
+                   residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_solve_form_f64`` (host-only): the form the float64 fused solve takes for this scene -- 0 the whole
+    image in LDS, 1 the scene read in place, 2 the vectors in the workspace too -- or a negative value where it
+    does not run."""
+    from ._ops import scene_struct_f64, solver_config_f64
+
+    sc = scene_struct_f64(None, None, num_views, num_points, distortion, batch, residual)
+    cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
+    return int(N.load_library().dava_ba_solve_form_f64(sc, cfg))
+
+
+def solve_large_workspace_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool,
+                                    iterations: int = 1000,
+                                    residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_solve_large_workspace_bytes_f64`` (host-only): the history rows, in form 2 the vectors too;
+    0 where the float64 fused solve does not run at any scene size."""
+    from ._ops import scene_struct_f64, solver_config_f64
+
+    sc = scene_struct_f64(None, None, num_views, num_points, distortion, batch, residual)
+    cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
+    return int(N.load_library().dava_ba_solve_large_workspace_bytes_f64(sc, cfg))
+
+
 def solve_plan(batch: int, num_views: int, num_points: int, distortion: bool,
                hessian_mode: int = N.DAVA_HESSIAN_DENSE, iterations: int = 1000,
                residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> dict:

@@ -202,9 +202,11 @@ int dava_ba_evaluate(const DavaScene* scene, const float* x, const float* direct
  * thresholds (1e-4 as a double is the reference's 1e-4), history rows.  COMPACT inverse Hessian only;
  * dava_ba_solve_f64 / dava_ba_solve_record_f64 run eval mode, training mode's drop path and
  * return_second_last go through dava_ba_solve_train_f64 / dava_ba_solve_record_train_f64 (DavaTrainingF64,
- * below).  One 256-thread workgroup per problem with its whole state in LDS: a shape is supported when
- * that image fits 160 KiB (C1-C3 do; C5 does not) and 1 <= iterations <= 1025.  Anything else:
- * DAVA_ERR_UNSUPPORTED, and 0 from the size query. */
+ * below).  One 256-thread workgroup per problem with its whole state in LDS: these entry points support a
+ * shape when that image fits 160 KiB (C1-C3 do; C5 does not) and 1 <= iterations <= 1025.  Anything else:
+ * DAVA_ERR_UNSUPPORTED, and 0 from the size query.  Scenes beyond the LDS image evaluate and solve through
+ * the `_large_f64` entry points further down; the recording solve, the adjoint and the second derivatives
+ * keep the limit. */
 typedef struct DavaSceneF64 {
   int32_t batch;               /* B >= 0                               */
   int32_t num_views;           /* M >= 2                               */
@@ -516,12 +518,47 @@ int dava_l1_camera_vjp_f64(int64_t batch, int32_t estimates, int32_t views, int3
                            double error_scale, const double* error_cotangent, const double* gradient_cotangent,
                            int32_t detach_points, double* input_cotangent_out, void* stream);
 
+/* ---- float64 evaluation and solve at any scene size (additive to ABI 4) ----
+ * The same kernels in three forms, chosen by what fits one workgroup's 160 KiB of LDS:
+ *   0  the whole image in LDS: the launch of dava_ba_solve[_train]_f64 / dava_ba_evaluate_f64;
+ *   1  observations and visibility read in place from device memory, the six O(P) vectors in LDS;
+ *   2  the scene in place and the vectors (x, d, g, g_prev / y, s, H'y) in a per-problem slice of the
+ *      workspace (the evaluation: x and direction in place, the gradient formed in grad_out's rows).
+ * Same algorithm, operation order, stopping rules, status words and training-mode semantics in every form;
+ * one workgroup per problem, which touches only its own slice.  No result depends on the workspace's previous
+ * contents.  Form 2 keeps its view constants and history scalars in LDS: more than 251 views at 1025
+ * iterations (361 for the evaluation) are DAVA_ERR_UNSUPPORTED.
+ *
+ * dava_ba_solve_form_f64: the form dava_ba_solve_large_f64 takes for this scene / config (host-only, no data
+ * pointers needed), or a negative value, minus the status dava_ba_solve_large_f64 would return, where none
+ * runs (invalid scene or config, iterations outside 1 .. 1025, ray angle with distortion). */
+int dava_ba_solve_form_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config);
+
+/* Bytes of device workspace dava_ba_solve_large_f64 needs, with Pv = round_up(P, 4):
+ *   the history rows   B * 2 * max(iterations - 1, 1) * Pv * 8
+ *   form 2 only        B * 6 * Pv * 8 of vectors, after the history rows
+ *   a 256-byte tail (unused, as in dava_ba_solve_workspace_bytes_f64).
+ * In form 0 this is dava_ba_solve_workspace_bytes_f64's figure.  0 where the solve does not run. */
+size_t dava_ba_solve_large_workspace_bytes_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config);
+
+/* dava_ba_solve_train_f64's contract for every scene dava_ba_solve_form_f64 accepts (training NULL or all
+ * zero: eval mode).  The host checks run in dava_ba_solve_f64's order; a workspace below the query's figure
+ * (needed whenever iterations > 1, and always in form 2) is DAVA_ERR_WORKSPACE before any launch. */
+int dava_ba_solve_large_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                            const DavaTrainingF64* training, const double* x0, double* x_out, double* error_out,
+                            int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dava_ba_evaluate_f64's contract at any N; no workspace.  In form 2 grad_out must not alias x or direction. */
+int dava_ba_evaluate_large_f64(const DavaSceneF64* scene, const double* x, const double* direction,
+                               const double* alpha, double* error_out, double* grad_out, double* slope_out,
+                               void* stream);
+
 /* ---- test and A/B hooks ----
  * The library makes its launch choices itself (LDS or global-vector mode, waves per workgroup,
  * on-chip history entries, work queue, ...) and reads NOTHING from the environment.  Tests and A/B
  * measurements override a choice by name (FORCE_GV, GV_NO_XL, SOLVE_WAVES, WG_PER_CU, LDS_HISTORY,
  * STAGGER, STAGGER_LEVELS, NO_PPT, NO_QUEUE, ADJ_GV_WAVES, ADJ_FORCE_GV, ADJ_LDS_ENTRIES, ADJ_GD_HBM,
- * COMPACT_SWITCH, GV_SCALAR_SLICE, ADJ_SC_GLOBAL; csrc/dava_debug.hpp); value < 0 restores the
+ * COMPACT_SWITCH, GV_SCALAR_SLICE, ADJ_SC_GLOBAL, F64_FORM; csrc/dava_debug.hpp); value < 0 restores the
  * library's choice.  Process-wide, not thread-safe, host-only.  DAVA_ERR_INVALID_ARGUMENT for an
  * unknown name.                                                                                   */
 int dava_debug_set_override(const char* name, int64_t value);

@@ -22,6 +22,14 @@ solve PLUS gradient through the drop-in on an objective built with float64_deriv
                  the same distribution; the mean steps per problem of the fused runs is reported.
   No rate is a requirement in this mode either.
 
+--large (default output profiles/f64_large.jsonl): the float64 solve beyond the LDS image (dava_ba_solve_large_f64),
+float64 and float32 fused alternated solve by solve in one process, K = 100 fixed iterations:
+  c5             C5 (16 x 4096, B = 256): float64 form 2 (scene in place, vectors in the workspace) against float32.
+  c3_forms       C3 (B = 8192): float64 form 0, and forms 1 and 2 forced through the F64_FORM override, against
+                 float32 -- what reading the scene in place, and the vectors from the workspace, cost where all run.
+  m6_n700        (6 x 700, Brown-Conrady, B = 1024): float64 form 1, the form it takes, against float32.
+  Every float64 run is checked: all problems finite, all took K steps.  No rate is a requirement.
+
 Timing: device events around each solve, every shape warmed up first, median of --repeats (>= 5) solves.
 Reported: problems/s, algorithmic HBM bytes (bench.py's compact model; 8-byte elements for float64, computed
 here), the fraction of 8 TB/s they amount to, and the ratio to the fp32 fused rate.  The one requirement
@@ -106,6 +114,62 @@ def fused_pair(tag, b, m, n, distortion, k, repeats, dev):
                      "algorithmic_bytes": algo, "fraction_of_8TBps": algo / med / PEAK_BYTES_PER_S,
                      "lds_history_entries": lds}
     out["f64_over_f32_rate"] = out["f64"]["problems_per_s"] / out["f32"]["problems_per_s"]
+    return out
+
+
+def large_forms(tag, b, m, n, distortion, k, repeats, dev, forms):
+    """float64 in each of `forms` (None: the form the fit chooses; 1 | 2: raised through F64_FORM) and float32 fused,
+    alternated solve by solve."""
+    from deep_attention_visual_odometry_amd import _native as N
+    from deep_attention_visual_odometry_amd import native_ops
+
+    x32, obs32, vis = scene(b, m, n, distortion, dev)
+    x64, obs64 = x32.double(), obs32.double()
+    p, mn = x32.shape[1], m * n
+    kw = dict(iterations=k, error_threshold=-1.0, minimum_step=-1.0, hessian_mode=N.DAVA_HESSIAN_COMPACT)
+    ws32 = torch.empty(native_ops.solve_workspace_bytes(b, m, n, distortion, N.DAVA_HESSIAN_COMPACT, k),
+                       dtype=torch.uint8, device=dev)
+    runs, taken, ws64 = {}, {}, {}
+
+    def f64_run(name, forced):
+        def run():
+            with N.debug_overrides(**({} if forced is None else {"F64_FORM": forced})):
+                return native_ops.ba_solve(x64, obs64, vis, m, n, distortion, workspace=ws64[name], want_status=True,
+                                           **kw)
+        return run
+
+    for forced in forms:
+        with N.debug_overrides(**({} if forced is None else {"F64_FORM": forced})):
+            form = native_ops.solve_form_f64(b, m, n, distortion, iterations=k)
+            need = native_ops.solve_large_workspace_bytes_f64(b, m, n, distortion, iterations=k)
+        name = f"f64_form{form}"
+        taken[name] = form
+        ws64[name] = torch.empty(need, dtype=torch.uint8, device=dev)
+        runs[name] = f64_run(name, forced)
+    runs["f32"] = lambda: native_ops.ba_solve(x32, obs32, vis, m, n, distortion, workspace=ws32, want_status=True, **kw)
+    checks = {}
+    for name, fn in runs.items():  # warm-up of every variant, and the check of its result
+        x, _, status = fn()
+        checks[name] = {"all_finite": bool(torch.isfinite(x).all().item()),
+                        "all_took_k_steps": bool((status[:, 0] == k).all().item())}
+    torch.cuda.synchronize()
+    times = {name: [] for name in runs}
+    for _ in range(repeats):
+        for name, fn in runs.items():
+            times[name] += timed(fn, 1)
+    lds_entries = native_ops.solve_plan(b, m, n, distortion, N.DAVA_HESSIAN_COMPACT, k)["lds_history_entries"]
+    out = {"config": tag, "batch": b, "views": m, "points": n, "distortion": distortion, "iterations": k,
+           "repeats": repeats, "device": torch.cuda.get_device_name(dev)}
+    for name in runs:
+        element, lds = (4, lds_entries) if name == "f32" else (8, 0)
+        med = statistics.median(times[name])
+        algo = b * compact_algorithmic_bytes(p, mn, k, element, lds)
+        out[name] = {"median_s": med, "min_s": min(times[name]), "max_s": max(times[name]), "problems_per_s": b / med,
+                     "algorithmic_bytes": algo, "fraction_of_8TBps": algo / med / PEAK_BYTES_PER_S, **checks[name]}
+        if name != "f32":
+            out[name]["form"] = taken[name]
+    for name in taken:
+        out[name]["over_f32_rate"] = out[name]["problems_per_s"] / out["f32"]["problems_per_s"]
     return out
 
 
@@ -262,6 +326,8 @@ def main(argv=None):
     ap.add_argument("--mode", choices=("solve", "grad", "train"), default="solve",
                     help="solve: the solve alone (the default); grad: solve plus gradient; train: training mode's "
                          "drop path, solve plus gradient")
+    ap.add_argument("--large", action="store_true",
+                    help="the float64 solve beyond the LDS image (forms 1 and 2) instead of --mode's runs")
     ap.add_argument("--out", default=None,
                     help="default: profiles/f64_solve.jsonl (solve), profiles/f64_adjoint.jsonl (grad), "
                          "profiles/f64_training.jsonl (train)")
@@ -270,6 +336,10 @@ def main(argv=None):
                                                      "c3_b32_k20,c2_b1024_k100 (train)")
     args = ap.parse_args(argv)
     grad, train = args.mode == "grad", args.mode == "train"
+    if args.large:
+        grad = train = False
+        args.out = args.out or os.path.join(REPO, "profiles", "f64_large.jsonl")
+        args.configs = args.configs or "c5,c3_forms,m6_n700"
     if args.out is None:
         args.out = os.path.join(REPO, "profiles", {"solve": "f64_solve.jsonl", "grad": "f64_adjoint.jsonl",
                                                    "train": "f64_training.jsonl"}[args.mode])
@@ -282,7 +352,15 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     lines, ok = [], True
     for name in args.configs.split(","):
-        if train and name == "c3_b32_k20":
+        if args.large and name == "c5":
+            lines.append(large_forms("large_c5", 256, 16, 4096, False, 100, args.repeats, dev, (None,)))
+        elif args.large and name == "c3_forms":
+            lines.append(large_forms("large_c3_forms", 8192, 4, 256, True, 100, args.repeats, dev, (None, 1, 2)))
+        elif args.large and name == "m6_n700":
+            lines.append(large_forms("large_m6_n700", 1024, 6, 700, True, 100, args.repeats, dev, (None,)))
+        elif args.large:
+            ap.error(f"unknown configuration {name!r} for --large")
+        elif train and name == "c3_b32_k20":
             lines.append(train_vs_generic(name, 32, 4, 256, True, 20, args.repeats, dev))
         elif train and name == "c2_b1024_k100":
             lines.append(train_vs_generic(name, 1024, 2, 128, False, 100, args.repeats, dev))
