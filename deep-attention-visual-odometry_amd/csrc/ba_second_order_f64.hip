@@ -4,8 +4,19 @@
 // E, dE/dx, H v + (d2E/dx dobs) u, dE/dobs and (d2E/dobs dx) v + (d2E/dobs2) u, one launch, one 256-thread
 // workgroup per problem with the dual image in LDS.  This is what the float64 objective's create_graph double
 // backward and the generic loop's graph through a float64 solve need (bfgs_solver.py:133-135).
+// Beyond the LDS image (dava_ba_second_order_large_f64) the same kernel body takes other pointers, FORM as in
+// solve_f64.hpp:
+//   form 0  the dual x and gradient, the dual dE/dobs, the observations and visibility in LDS
+//   form 1  the dual x and gradient in LDS; the scene read in place; the dual dE/dobs (written per pair by its
+//           owner thread) in a workspace of B x 4MN doubles, split into the two outputs after the evaluation's
+//           final barrier -- not formed when neither output is asked for
+//   form 2  as form 1, the dual x and gradient in a per-problem workspace slice of 4 Pv doubles
+// Workspace: [dual dE/dobs B x 4MN, if an observation output is asked for | form 2: B x 4 Pv | 256-byte tail].
 #include "ba_objective.hpp"
+#include "dava_debug.hpp"
 #include "dava_f64.hpp"
+
+#include <type_traits>
 
 namespace dava {
 namespace f64 {
@@ -19,6 +30,15 @@ struct SecondArgs {
   const uint8_t* vis;
   double *err, *grad, *hv, *obs_grad, *obs_hv;
 };
+
+// What the form 1 and 2 instantiations take (the form-0 one keeps its kernel argument as it was)
+struct LargeSecondArgs : SecondArgs {
+  double* obsd;  // B x 4MN (Dual64 dE/dobs), or null: not formed
+  double* vecs;  // form 2: B x 4 Pv (Dual64 x, g), uninitialised
+};
+
+template <int FORM>
+using second_args_t = std::conditional_t<FORM != 0, LargeSecondArgs, SecondArgs>;
 
 struct SecondCarve {
   int x, g, views, vpart, obsd, scratch, obs, vis_bytes_off;  // offsets in doubles
@@ -43,28 +63,67 @@ __host__ __device__ inline SecondCarve carve_second(int M, int N, int Pv) {
   return c;
 }
 
-template <int RES>
-__global__ __launch_bounds__(kBlock, 1) void ba_second_order_f64_kernel(SecondArgs a) {
+// The LDS image of forms 1 and 2: no scene, no dE/dobs and in form 2 no x / g either.  x and g are relative to
+// the vectors' base (LDS, or the problem's slice), the others to the LDS base.
+__host__ __device__ inline SecondCarve carve_second_large(int M, int Pv, int form) {
+  SecondCarve c{};
+  const long long doubles = (form == 1 ? 4LL * Pv : 0) + 2LL * views_floats(M) + 2LL * vpart_floats(M) + 2 * kWaves * 32;
+  c.total_bytes = doubles * 8;
+  if (c.total_bytes > kMaxLdsBytes) return c;
+  int off = 0;
+  c.x = off; off += 2 * Pv;
+  c.g = off; off += 2 * Pv;
+  if (form != 1) off = 0;
+  c.views = off; off += 2 * views_floats(M);
+  c.vpart = off; off += 2 * vpart_floats(M);
+  c.scratch = off; off += 2 * kWaves * 32;
+  return c;
+}
+
+// The form a scene takes: the lowest whose image fits, raised (never lowered) by the F64_FORM override; -1 where
+// not even form 2's image (the dual view constants and partials) fits.
+inline int choose_second_form(int M, int N, int Pv) {
+  int form = 2;
+  if (carve_second(M, N, Pv).total_bytes <= kMaxLdsBytes) form = 0;
+  else if (carve_second_large(M, Pv, 1).total_bytes <= kMaxLdsBytes) form = 1;
+  const long long forced = debug_knob(kDbgF64Form);
+  if ((forced == 1 || forced == 2) && forced > form) form = (int)forced;
+  if (form == 2 && carve_second_large(M, Pv, 2).total_bytes > kMaxLdsBytes) return -1;
+  return form;
+}
+
+template <int RES, int FORM = 0>
+__global__ __launch_bounds__(kBlock, 1) void ba_second_order_f64_kernel(second_args_t<FORM> a) {
   extern __shared__ __attribute__((aligned(16))) double lds64[];
   const Layout L = a.L;
   const int P = L.P, M = L.M, N = L.N, MN = M * N;
   const int tid = threadIdx.x;
   const size_t b = blockIdx.x;
-  const SecondCarve cv = carve_second(M, N, a.Pv);
-  Dual64* x = reinterpret_cast<Dual64*>(lds64 + cv.x);
-  Dual64* g = reinterpret_cast<Dual64*>(lds64 + cv.g);
+  const SecondCarve cv = FORM == 0 ? carve_second(M, N, a.Pv) : carve_second_large(M, a.Pv, FORM);
+  double* vec = lds64;  // the dual x and gradient: LDS, or (form 2) this problem's workspace slice
+  if constexpr (FORM == 2) vec = a.vecs + b * 4 * a.Pv;
+  Dual64* x = reinterpret_cast<Dual64*>(vec + cv.x);
+  Dual64* g = reinterpret_cast<Dual64*>(vec + cv.g);
   Dual64* views = reinterpret_cast<Dual64*>(lds64 + cv.views);
   Dual64* vpart = reinterpret_cast<Dual64*>(lds64 + cv.vpart);
   Dual64* obsd = reinterpret_cast<Dual64*>(lds64 + cv.obsd);
+  if constexpr (FORM != 0) obsd = a.obsd ? reinterpret_cast<Dual64*>(a.obsd + b * 4 * MN) : nullptr;
   double* scratch = lds64 + cv.scratch;
-  double* obs = lds64 + cv.obs;
-  uint8_t* vis = reinterpret_cast<uint8_t*>(lds64) + cv.vis_bytes_off;
+  double* obl = lds64 + cv.obs;  // form 0: the scene's LDS copy
+  uint8_t* vil = reinterpret_cast<uint8_t*>(lds64) + cv.vis_bytes_off;
+  const double* obs = obl;
+  const uint8_t* vis = vil;
   for (int i = tid; i < a.Pv; i += kBlock) {
     x[i] = i < P ? Dual64(a.x[b * P + i], a.v ? a.v[b * P + i] : 0.0) : Dual64(0.0);
     g[i] = Dual64(0.0);
   }
-  for (int i = tid; i < 2 * MN; i += kBlock) obs[i] = a.obs[b * 2 * MN + i];
-  for (int i = tid; i < MN; i += kBlock) vis[i] = a.vis[b * MN + i] ? 1 : 0;
+  if constexpr (FORM == 0) {
+    for (int i = tid; i < 2 * MN; i += kBlock) obl[i] = a.obs[b * 2 * MN + i];
+    for (int i = tid; i < MN; i += kBlock) vil[i] = a.vis[b * MN + i] ? 1 : 0;
+  } else {  // the scene where the caller put it
+    obs = a.obs + b * 2 * MN;
+    vis = a.vis + b * MN;
+  }
   __syncthreads();
   int buf = 0;
   Dual64 E(0.0), unused(0.0);
@@ -77,9 +136,11 @@ __global__ __launch_bounds__(kBlock, 1) void ba_second_order_f64_kernel(SecondAr
     if (a.hv) a.hv[b * P + i] = g[i].t;
   }
   // dE/dobs was written per (view, point) pair by its owner thread; the eval's final barrier makes it visible
-  for (int i = tid; i < 2 * MN; i += kBlock) {
-    if (a.obs_grad) a.obs_grad[b * 2 * MN + i] = obsd[i].v;
-    if (a.obs_hv) a.obs_hv[b * 2 * MN + i] = obsd[i].t;
+  if (FORM == 0 || obsd) {
+    for (int i = tid; i < 2 * MN; i += kBlock) {
+      if (a.obs_grad) a.obs_grad[b * 2 * MN + i] = obsd[i].v;
+      if (a.obs_hv) a.obs_hv[b * 2 * MN + i] = obsd[i].t;
+    }
   }
 }
 
@@ -122,5 +183,88 @@ extern "C" int dava_ba_second_order_f64(const DavaSceneF64* scene, const double*
   const int lds = (int)cv.total_bytes;
   if (sc.residual == DAVA_RESIDUAL_RAY_ANGLE) f64::launch_second<DAVA_RESIDUAL_RAY_ANGLE>(a, sc.batch, lds, s);
   else f64::launch_second<DAVA_RESIDUAL_SQUARED_REPROJECTION>(a, sc.batch, lds, s);
+  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+}
+
+namespace {
+
+template <int FORM>
+void launch_second_large(const f64::LargeSecondArgs& a, int B, int lds, hipStream_t s, bool ray) {
+  auto go = [&](auto kernel) {
+    set_dynamic_lds(kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(kBlock), lds, s, a);
+  };
+  if (ray) go(f64::ba_second_order_f64_kernel<DAVA_RESIDUAL_RAY_ANGLE, FORM>);
+  else go(f64::ba_second_order_f64_kernel<DAVA_RESIDUAL_SQUARED_REPROJECTION, FORM>);
+}
+
+size_t second_obsd_bytes(const DavaScene& sc) {
+  return (size_t)sc.batch * 4 * sc.num_views * sc.num_points * sizeof(double);
+}
+
+size_t second_vector_bytes(const DavaScene& sc) {
+  return (size_t)sc.batch * 4 * round_up(sc.num_parameters, 4) * sizeof(double);
+}
+
+}  // namespace
+
+// host-only: 0, 1, 2, or minus the status
+extern "C" int dava_ba_second_order_form_f64(const DavaSceneF64* scene) {
+  DavaScene sc;
+  const int st = f64::check_scene_f64(scene, false, sc);
+  if (st != DAVA_OK) return -st;
+  const int form = f64::choose_second_form(sc.num_views, sc.num_points, round_up(sc.num_parameters, 4));
+  return form < 0 ? -DAVA_ERR_UNSUPPORTED : form;
+}
+
+// host-only; obs_outputs: an observation output (obs_grad_out or obs_hv_out) will be asked for.  0: unsupported.
+extern "C" size_t dava_ba_second_order_large_workspace_bytes_f64(const DavaSceneF64* scene, int obs_outputs) {
+  DavaScene sc;
+  if (f64::check_scene_f64(scene, false, sc) != DAVA_OK) return 0;
+  const int form = f64::choose_second_form(sc.num_views, sc.num_points, round_up(sc.num_parameters, 4));
+  if (form < 0) return 0;
+  return (form != 0 && obs_outputs ? second_obsd_bytes(sc) : 0) + (form == 2 ? second_vector_bytes(sc) : 0) +
+         f64::kTailBytes;
+}
+
+extern "C" int dava_ba_second_order_large_f64(const DavaSceneF64* scene, const double* x, const double* direction,
+                                              const double* obs_direction, double* error_out, double* grad_out,
+                                              double* hv_out, double* obs_grad_out, double* obs_hv_out,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+  DavaScene sc;
+  const int st = f64::check_scene_f64(scene, true, sc);
+  if (st != DAVA_OK) return st;
+  if (sc.batch == 0) return DAVA_OK;
+  if (!x) return DAVA_ERR_INVALID_ARGUMENT;
+  const int Pv = round_up(sc.num_parameters, 4);
+  const int form = f64::choose_second_form(sc.num_views, sc.num_points, Pv);
+  if (form < 0) return DAVA_ERR_UNSUPPORTED;
+  if (form == 0)  // the whole image fits LDS: the launch of dava_ba_second_order_f64
+    return dava_ba_second_order_f64(scene, x, direction, obs_direction, error_out, grad_out, hv_out, obs_grad_out,
+                                    obs_hv_out, stream);
+  const bool obs_out = obs_grad_out || obs_hv_out;
+  const size_t obsd_bytes = obs_out ? second_obsd_bytes(sc) : 0;
+  const size_t need = obsd_bytes + (form == 2 ? second_vector_bytes(sc) : 0);
+  if (need > 0 && (!workspace || workspace_bytes < need + f64::kTailBytes)) return DAVA_ERR_WORKSPACE;
+  f64::LargeSecondArgs a;
+  a.L = make_layout(&sc);
+  a.Pv = Pv;
+  a.obs = scene->observations;
+  a.vis = scene->visibility;
+  a.x = x;
+  a.v = direction;
+  a.obs_v = obs_direction;
+  a.err = error_out;
+  a.grad = grad_out;
+  a.hv = hv_out;
+  a.obs_grad = obs_grad_out;
+  a.obs_hv = obs_hv_out;
+  a.obsd = obs_out ? static_cast<double*>(workspace) : nullptr;
+  a.vecs = form == 2 ? reinterpret_cast<double*>(static_cast<char*>(workspace) + obsd_bytes) : nullptr;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int lds = (int)f64::carve_second_large(sc.num_views, Pv, form).total_bytes;
+  const bool ray = sc.residual == DAVA_RESIDUAL_RAY_ANGLE;
+  if (form == 1) launch_second_large<1>(a, sc.batch, lds, s, ray);
+  else launch_second_large<2>(a, sc.batch, lds, s, ray);
   return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
 }

@@ -9,8 +9,11 @@
 // Workspace of the solve: [history B x (S[kcap][Pv], W[kcap][Pv]) | form 2: vectors B x 6 x Pv | 256-byte tail],
 // doubles.  The vector slices arrive uninitialised: the kernel writes all 6 x Pv doubles of its slice, pads
 // included, before it reads any.
-// Not here: the recording solve, the adjoint and the second derivatives keep the LDS image's limit;
-// no LDS copies of x or d for a form-2 problem, no lean trials, no on-chip history entries, no dense / hybrid mode.
+// The recording solve in forms 1 and 2 (dava_ba_solve_record_large_f64, dava_ba_solve_tape_bytes_large_f64,
+// dava_ba_solve_record_large_workspace_bytes_f64) is the same kernel with RECORD: the tape (dava_tape.hpp in doubles,
+// the layout of every form) is its history workspace, and form 2's vector slices come from a workspace of their own:
+// [vectors B x 6 x Pv | 256-byte tail].
+// Not here: no LDS copies of x or d for a form-2 problem, no lean trials, no on-chip history entries, no dense / hybrid mode.
 #include "solve_f64.hpp"
 
 using namespace dava;
@@ -37,13 +40,21 @@ size_t large_workspace_bytes(const DavaScene& sc, int iterations, int form) {
 }
 
 template <int FORM>
-void launch_solve(const f64::LargeArgs& a, int lds, hipStream_t s, bool ray, bool train) {
+void launch_solve(const f64::LargeArgs& a, int lds, hipStream_t s, bool ray, bool train, bool record = false) {
   auto go = [&](auto kernel) {
     set_dynamic_lds(kernel, lds);
     hipLaunchKernelGGL(kernel, dim3(a.B), dim3(kBlock), lds, s, a);
   };
   constexpr int kRay = DAVA_RESIDUAL_RAY_ANGLE, kSq = DAVA_RESIDUAL_SQUARED_REPROJECTION;
-  if (train) {
+  if (record) {
+    if (train) {
+      if (ray) go(f64::bfgs_ba_solve_f64_kernel<kRay, true, true, FORM>);
+      else go(f64::bfgs_ba_solve_f64_kernel<kSq, true, true, FORM>);
+    } else {
+      if (ray) go(f64::bfgs_ba_solve_f64_kernel<kRay, true, false, FORM>);
+      else go(f64::bfgs_ba_solve_f64_kernel<kSq, true, false, FORM>);
+    }
+  } else if (train) {
     if (ray) go(f64::bfgs_ba_solve_f64_kernel<kRay, false, true, FORM>);
     else go(f64::bfgs_ba_solve_f64_kernel<kSq, false, true, FORM>);
   } else {
@@ -71,11 +82,14 @@ extern "C" size_t dava_ba_solve_large_workspace_bytes_f64(const DavaSceneF64* sc
   return large_workspace_bytes(sc, config->iterations, form);
 }
 
+namespace {
+
+// dava_ba_solve_large_f64 (tape == null: `workspace` holds the history rows and form 2's vectors) and
+// dava_ba_solve_record_large_f64 (the tape's first block is the history rows; `workspace` holds form 2's vectors).
 // The host checks of f64::solve_lds in its order; training: null or all zero = eval mode.
-extern "C" int dava_ba_solve_large_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
-                                       const DavaTrainingF64* training, const double* x0, double* x_out,
-                                       double* error_out, int32_t* status_out, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
+int solve_large(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const DavaTrainingF64* training,
+                const double* x0, double* x_out, double* error_out, int32_t* status_out, void* tape,
+                size_t tape_bytes, bool record, void* workspace, size_t workspace_bytes, void* stream) {
   if (training && !(training->drop_path_p >= 0.f && training->drop_path_p <= 1.f)) return DAVA_ERR_INVALID_ARGUMENT;
   const bool train = training && (training->drop_path_p > 0.f || training->return_second_last);
   DavaScene sc;
@@ -87,12 +101,21 @@ extern "C" int dava_ba_solve_large_f64(const DavaSceneF64* scene, const DavaSolv
   if (sc.batch == 0) return DAVA_OK;
   if (!x0 || !x_out) return DAVA_ERR_INVALID_ARGUMENT;
   if (sup != DAVA_OK) return sup;
-  if (form == 0)  // the whole image fits LDS: the launch of dava_ba_solve[_train]_f64
-    return f64::solve_lds(scene, config, training, x0, x_out, error_out, status_out, workspace, workspace_bytes,
-                          false, stream);
-  const bool uses_ws = form == 2 || config->iterations > 1;
-  if (uses_ws && (!workspace || workspace_bytes < large_workspace_bytes(sc, config->iterations, form)))
-    return DAVA_ERR_WORKSPACE;  // (the size the query reports, tail included)
+  if (form == 0)  // the whole image fits LDS: the launch of dava_ba_solve[_record][_train]_f64
+    return record ? f64::solve_lds(scene, config, training, x0, x_out, error_out, status_out, tape, tape_bytes, true,
+                                   stream)
+                  : f64::solve_lds(scene, config, training, x0, x_out, error_out, status_out, workspace,
+                                   workspace_bytes, false, stream);
+  const TapeLayout tl = tape_layout_f64(sc.batch, sc.num_parameters, config->iterations);
+  if (record) {
+    if (!status_out) return DAVA_ERR_INVALID_ARGUMENT;
+    if (!tape || tape_bytes < tl.total_bytes) return DAVA_ERR_WORKSPACE;
+    if (form == 2 && (!workspace || workspace_bytes < vector_bytes(sc) + f64::kTailBytes)) return DAVA_ERR_WORKSPACE;
+  } else {
+    const bool uses_ws = form == 2 || config->iterations > 1;
+    if (uses_ws && (!workspace || workspace_bytes < large_workspace_bytes(sc, config->iterations, form)))
+      return DAVA_ERR_WORKSPACE;  // (the size the query reports, tail included)
+  }
   f64::LargeArgs a;
   a.L = make_layout(&sc);
   a.B = sc.batch;
@@ -104,7 +127,7 @@ extern "C" int dava_ba_solve_large_f64(const DavaSceneF64* scene, const DavaSolv
   a.x_out = x_out;
   a.err_out = error_out;
   a.status = status_out;
-  a.hist = config->iterations > 1 ? static_cast<double*>(workspace) : nullptr;
+  a.hist = record ? static_cast<double*>(tape) : config->iterations > 1 ? static_cast<double*>(workspace) : nullptr;
   a.c1 = config->sufficient_decrease;
   a.c2 = config->curvature;
   a.thr = config->error_threshold;
@@ -112,19 +135,58 @@ extern "C" int dava_ba_solve_large_f64(const DavaSceneF64* scene, const DavaSolv
   a.iters = config->iterations;
   a.max_trials = config->max_line_search_trials;
   a.strong = config->strong_wolfe;
-  a.tape_x = a.tape_g = a.tape_sc = a.tape_tail = nullptr;
-  a.T = 0;
+  a.tape_x = record ? static_cast<double*>(tape) + tl.x : nullptr;
+  a.tape_g = record ? static_cast<double*>(tape) + tl.g : nullptr;
+  a.tape_sc = record ? static_cast<double*>(tape) + tl.scal : nullptr;
+  a.tape_tail = record ? static_cast<double*>(tape) + tl.vecs : nullptr;
+  a.T = record ? tl.T : 0;
   a.drop_p = train ? training->drop_path_p : 0.f;
   a.drop_seed = train ? ((unsigned long long)training->drop_seed_hi << 32) | training->drop_seed_lo : 0ull;
   a.second_last = train && training->return_second_last ? 1 : 0;
-  a.vecs = form == 2 ? reinterpret_cast<double*>(static_cast<char*>(workspace) + f64::history_bytes(sc, a.iters))
-                     : nullptr;
+  a.vecs = form != 2 ? nullptr
+           : record  ? static_cast<double*>(workspace)
+                     : reinterpret_cast<double*>(static_cast<char*>(workspace) + f64::history_bytes(sc, a.iters));
   const int lds = (int)f64::carve_large(sc.num_views, a.Pv, a.kcap, form).total_bytes;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool ray = sc.residual == DAVA_RESIDUAL_RAY_ANGLE;
-  if (form == 1) launch_solve<1>(a, lds, s, ray, train);
-  else launch_solve<2>(a, lds, s, ray, train);
+  if (form == 1) launch_solve<1>(a, lds, s, ray, train, record);
+  else launch_solve<2>(a, lds, s, ray, train, record);
   return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+}
+
+}  // namespace
+
+extern "C" int dava_ba_solve_large_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                                       const DavaTrainingF64* training, const double* x0, double* x_out,
+                                       double* error_out, int32_t* status_out, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  return solve_large(scene, config, training, x0, x_out, error_out, status_out, nullptr, 0, false, workspace,
+                     workspace_bytes, stream);
+}
+
+extern "C" size_t dava_ba_solve_tape_bytes_large_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config) {
+  DavaScene sc;
+  int form = -1;
+  if (f64::check_scene_f64(scene, false, sc) != DAVA_OK) return 0;
+  if (large_supported(sc, config, form) != DAVA_OK) return 0;
+  return tape_layout_f64(sc.batch, sc.num_parameters, config->iterations).total_bytes;
+}
+
+extern "C" size_t dava_ba_solve_record_large_workspace_bytes_f64(const DavaSceneF64* scene,
+                                                                 const DavaSolverConfigF64* config) {
+  DavaScene sc;
+  int form = -1;
+  if (f64::check_scene_f64(scene, false, sc) != DAVA_OK) return 0;
+  if (large_supported(sc, config, form) != DAVA_OK) return 0;
+  return form == 2 ? vector_bytes(sc) + f64::kTailBytes : 0;
+}
+
+extern "C" int dava_ba_solve_record_large_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                                              const DavaTrainingF64* training, const double* x0, double* x_out,
+                                              double* error_out, int32_t* status_out, void* tape, size_t tape_bytes,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+  return solve_large(scene, config, training, x0, x_out, error_out, status_out, tape, tape_bytes, true, workspace,
+                     workspace_bytes, stream);
 }
 
 extern "C" int dava_ba_evaluate_large_f64(const DavaSceneF64* scene, const double* x, const double* direction,

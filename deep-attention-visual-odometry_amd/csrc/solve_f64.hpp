@@ -146,10 +146,9 @@ __device__ __forceinline__ void eval(const Layout& L, const double* x, const dou
 // code they were without the flag.
 // FORM (the header's list): where x, d, g, g_prev / y, s, H'y and the scene live.  It changes only the pointers the
 // body below is given, so the compiler knows each one's address space; the arithmetic, the reduction trees and the
-// pass order are one text for the three forms.  RECORD exists in form 0 only.
+// pass order are one text for the three forms.  RECORD adds stores only and no LDS, so it exists in every form.
 template <int RES, bool RECORD, bool TRAIN, int FORM = 0>
 __global__ __launch_bounds__(kBlock, 1) void bfgs_ba_solve_f64_kernel(solve_args_t<TRAIN, FORM> a) {
-  static_assert(FORM == 0 || !RECORD, "the recording solve keeps its whole image in LDS");
   extern __shared__ __attribute__((aligned(16))) double lds64[];
   const Layout L = a.L;
   const int P = L.P, M = L.M, N = L.N, Pv = a.Pv;

@@ -156,6 +156,29 @@ SIGNATURES = {
                                                ctypes.POINTER(DavaTrainingF64), _vp, _vp, _vp, _vp, _vp,
                                                ctypes.c_size_t, _vp]),
     "dava_ba_evaluate_large_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # float64 gradients beyond the LDS image: recording solve, adjoint and second derivatives in forms 1 and 2
+    "dava_ba_solve_tape_bytes_large_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                             ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_record_large_workspace_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                                         ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_record_large_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64),
+                                                      ctypes.POINTER(DavaSolverConfigF64),
+                                                      ctypes.POINTER(DavaTrainingF64), _vp, _vp, _vp, _vp, _vp,
+                                                      ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "dava_ba_solve_backward_form_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64),
+                                                       ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_backward_large_workspace_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                                           ctypes.POINTER(DavaSolverConfigF64)]),
+    "dava_ba_solve_backward_large_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64),
+                                                        ctypes.POINTER(DavaSolverConfigF64), _vp, ctypes.c_size_t,
+                                                        _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dava_ba_second_order_form_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64)]),
+    "dava_ba_second_order_large_workspace_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64), ctypes.c_int]),
+    "dava_ba_second_order_large_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64)] + [_vp] * 9
+                                       + [ctypes.c_size_t, _vp]),
+    "dava_bfgs_update_inverse_hessian_backward_large_workspace_bytes_f64": (ctypes.c_size_t, [_c_i64, _c_i64]),
+    "dava_bfgs_update_inverse_hessian_backward_large_f64": (ctypes.c_int, [_c_i64, _c_i64] + [_vp] * 8
+                                                            + [ctypes.c_size_t, _vp]),
     "dava_ba_second_order": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 8),
     "dava_ba_second_order_obs": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 9),
     "dava_ba_solve_tape_bytes": (ctypes.c_size_t, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSolverConfig)]),

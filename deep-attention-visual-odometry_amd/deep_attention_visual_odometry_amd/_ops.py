@@ -524,6 +524,149 @@ def _(x_out_grad, tape, status, observations, visibility, num_views, num_points,
             torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
 
 
+# ---------------------------------------- float64 gradients beyond the LDS image (forms 1 and 2)
+# Operators of their own (`*_large_f64`): the three above keep their limits and error texts, and keep ignoring the
+# F64_FORM override.  These take any scene size -- a scene whose image fits runs the launch of the symbols above.
+
+def _scratch(need: int, dev) -> Tensor:
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    if _POISON:
+        ws.fill_(0xFF)
+    return ws
+
+
+@torch.library.custom_op("dava::ba_second_order_large_f64", mutates_args=(), device_types=_CUDA)
+def ba_second_order_large_f64(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
+                              distortion: bool, direction: Optional[Tensor], residual: int, want_hv: bool,
+                              want_obs: bool,
+                              obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``dava_ba_second_order_large_f64``: ``ba_second_order_f64`` for a scene of any size."""
+    lib = N.load_library()
+    _require_float64(x, "the float64 second derivatives")
+    _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
+    _same_f64(direction, x, "direction")
+    _same_f64(obs_direction, observations, "obs_direction")
+    b = x.shape[0]
+    err = torch.empty(b, device=x.device, dtype=torch.float64)
+    grad = torch.empty_like(x)
+    hv = torch.empty_like(x) if want_hv else _empty0(x)
+    obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
+    obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
+    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+    need = int(lib.dava_ba_second_order_large_workspace_bytes_f64(sc, 1 if want_obs else 0))
+    if need == 0:
+        raise ValueError("this scene has no float64 second derivatives (more views than the dual view constants "
+                         "can hold in LDS)")
+    ws = _scratch(need, x.device)
+    with torch.cuda.device(x.device):
+        N.check(lib.dava_ba_second_order_large_f64(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err),
+                                                   N.ptr(grad), N.ptr(hv) if want_hv else None,
+                                                   N.ptr(obs_grad) if want_obs else None,
+                                                   N.ptr(obs_hv) if (want_obs and want_hv) else None, N.ptr(ws),
+                                                   ws.numel(), N.stream_of(x.device)),
+                "dava_ba_second_order_large_f64")
+    return err, grad, hv, obs_grad, obs_hv
+
+
+@ba_second_order_large_f64.register_fake
+def _(x, observations, visibility, num_views, num_points, distortion, direction, residual, want_hv, want_obs,
+      obs_direction=None):
+    b = x.shape[0]
+    return (x.new_empty((b,)), torch.empty_like(x), torch.empty_like(x) if want_hv else x.new_empty((0,)),
+            torch.empty_like(observations) if want_obs else x.new_empty((0,)),
+            torch.empty_like(observations) if (want_obs and want_hv) else x.new_empty((0,)))
+
+
+@torch.library.custom_op("dava::ba_solve_record_large_f64", mutates_args=(), device_types=_CUDA)
+def ba_solve_record_large_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
+                              distortion: bool, sufficient_decrease: float, curvature: float, error_threshold: float,
+                              iterations: int, minimum_step: float, max_line_search_trials: int, strong: bool,
+                              residual: int, want_error: bool = False, drop_path_p: float = 0.0, drop_seed: int = 0,
+                              return_second_last: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``dava_ba_solve_record_large_f64``: ``ba_solve_record_f64`` for a scene of any size (the same tape).
+    Returns (x, status (B, 4) int32, tape uint8, error (B,) or empty)."""
+    lib = N.load_library()
+    _require_float64(x0, "the float64 recording solve")
+    _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
+    b, dev = x0.shape[0], x0.device
+    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+    cfg = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
+                            max_line_search_trials, strong)
+    train = training_f64(drop_path_p, drop_seed, return_second_last)
+    need = int(lib.dava_ba_solve_tape_bytes_large_f64(sc, cfg))
+    if need == 0:
+        raise ValueError("this scene / configuration has no float64 fused solve (1 <= iterations <= 1025, "
+                         "at most 251 views at 1025 iterations)")
+    tape = torch.empty(need, dtype=torch.uint8, device=dev)
+    if _POISON:
+        tape.fill_(0xFF)
+    ws = _scratch(int(lib.dava_ba_solve_record_large_workspace_bytes_f64(sc, cfg)), dev)
+    x_out = torch.empty_like(x0)
+    err = torch.empty(b, device=dev, dtype=torch.float64) if want_error else _empty0(x0)
+    status = torch.empty((b, N.STATUS_WORDS), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        N.check(lib.dava_ba_solve_record_large_f64(sc, cfg, train, N.ptr(x0), N.ptr(x_out),
+                                                   N.ptr(err) if want_error else None, N.ptr(status), N.ptr(tape),
+                                                   tape.numel(), N.ptr(ws), ws.numel(), N.stream_of(dev)),
+                "dava_ba_solve_record_large_f64")
+    return x_out, status, tape, err
+
+
+@ba_solve_record_large_f64.register_fake
+def _(x0, observations, visibility, num_views, num_points, distortion, sufficient_decrease, curvature,
+      error_threshold, iterations, minimum_step, max_line_search_trials, strong, residual, want_error=False,
+      drop_path_p=0.0, drop_seed=0, return_second_last=False):
+    b = x0.shape[0]
+    return (torch.empty_like(x0), x0.new_empty((b, N.STATUS_WORDS), dtype=torch.int32),
+            x0.new_empty((tape_bytes_f64(b, x0.shape[1], iterations),), dtype=torch.uint8),
+            x0.new_empty((b,) if want_error else (0,)))
+
+
+@torch.library.custom_op("dava::ba_solve_backward_large_f64", mutates_args=(), device_types=_CUDA)
+def ba_solve_backward_large_f64(x_out_grad: Tensor, tape: Tensor, status: Tensor, observations: Tensor,
+                                visibility: Tensor, num_views: int, num_points: int, distortion: bool,
+                                iterations: int, residual: int, want_observations: bool) -> Tuple[Tensor, Tensor]:
+    """``dava_ba_solve_backward_large_f64``: ``ba_solve_backward_f64`` for a scene of any size."""
+    lib = N.load_library()
+    _require_float64(x_out_grad, "the float64 fused solve's adjoint")
+    _check_scene_tensors(x_out_grad, observations, visibility, num_views, num_points, distortion)
+    b, dev = x_out_grad.shape[0], x_out_grad.device
+    if tuple(status.shape) != (b, N.STATUS_WORDS) or status.dtype != torch.int32 or not status.is_contiguous():
+        raise ValueError("status must be the recording call's contiguous (B, 4) int32 tensor")
+    for what, t in (("tape", tape), ("status", status)):
+        if t.device != dev:
+            raise ValueError(f"{what} must be on {dev} (the cotangent's device), got {t.device}")
+    if tape.dtype != torch.uint8 or tape.dim() != 1 or not tape.is_contiguous():
+        raise ValueError("tape must be the recording call's contiguous 1-D uint8 tensor")
+    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+    cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
+    tape_need = int(lib.dava_ba_solve_tape_bytes_large_f64(sc, cfg))
+    need = int(lib.dava_ba_solve_backward_large_workspace_bytes_f64(sc, cfg))
+    if need == 0 or tape_need == 0:
+        raise ValueError("this scene / configuration has no float64 fused adjoint (1 <= iterations <= 1025, the "
+                         "dual view constants must fit LDS)")
+    if tape.numel() < tape_need:
+        raise ValueError(f"tape holds {tape.numel()} bytes; a recording of this scene and iteration count "
+                         f"writes {tape_need}")
+    ws = _scratch(need, dev)
+    gx = torch.empty_like(x_out_grad)
+    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
+    with torch.cuda.device(dev):
+        N.check(lib.dava_ba_solve_backward_large_f64(sc, cfg, N.ptr(tape), tape.numel(), N.ptr(status),
+                                                     N.ptr(x_out_grad), N.ptr(gx),
+                                                     N.ptr(gobs) if want_observations else None, N.ptr(ws),
+                                                     ws.numel(), N.stream_of(dev)),
+                "dava_ba_solve_backward_large_f64")
+    return gx, gobs
+
+
+@ba_solve_backward_large_f64.register_fake
+def _(x_out_grad, tape, status, observations, visibility, num_views, num_points, distortion, iterations, residual,
+      want_observations):
+    return (torch.empty_like(x_out_grad),
+            torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
+
+
 # ------------------------------------------------- generic BFGS building blocks
 
 def _square_batch(h: Tensor) -> Tuple[int, int]:
@@ -567,6 +710,9 @@ def _(h, s, y):
     return torch.empty_like(h)
 
 
+_UPDATE_BACKWARD_VECTORS, _UPDATE_BACKWARD_LDS_BYTES = 9, 150 * 1024  # update_backward (csrc/bfgs_grad.hip)
+
+
 @torch.library.custom_op("dava::bfgs_update_inverse_hessian_backward", mutates_args=(), device_types=_CUDA)
 def bfgs_update_inverse_hessian_backward(h: Tensor, s: Tensor, y: Tensor, grad: Tensor, need_h: bool, need_s: bool,
                                          need_y: bool) -> Tuple[Tensor, Tensor, Tensor]:
@@ -575,11 +721,21 @@ def bfgs_update_inverse_hessian_backward(h: Tensor, s: Tensor, y: Tensor, grad: 
     gh = torch.empty_like(h) if need_h else _empty0(h)
     gs = torch.empty_like(s) if need_s else _empty0(h)
     gy = torch.empty_like(y) if need_y else _empty0(h)
+    lib = N.load_library()
+    outs = (N.ptr(gh) if need_h else None, N.ptr(gs) if need_s else None, N.ptr(gy) if need_y else None)
     with torch.cuda.device(h.device):
-        N.check(getattr(N.load_library(), f"dava_bfgs_update_inverse_hessian_backward_{_dt(h)}")(
-            b, n, N.ptr(h), N.ptr(s), N.ptr(y), N.ptr(grad), N.ptr(gh) if need_h else None,
-            N.ptr(gs) if need_s else None, N.ptr(gy) if need_y else None, N.stream_of(h.device)),
-            "dava_bfgs_update_inverse_hessian_backward")
+        if h.dtype == torch.float64 and _UPDATE_BACKWARD_VECTORS * n * 8 > _UPDATE_BACKWARD_LDS_BYTES:
+            # beyond the LDS image of the float64 kernel (n > 2133): its nine vectors in a workspace
+            ws = torch.empty(b * _UPDATE_BACKWARD_VECTORS * n * 8 + 256, dtype=torch.uint8, device=h.device)
+            if _POISON:
+                ws.fill_(0xFF)
+            N.check(lib.dava_bfgs_update_inverse_hessian_backward_large_f64(
+                b, n, N.ptr(h), N.ptr(s), N.ptr(y), N.ptr(grad), *outs, N.ptr(ws), ws.numel(),
+                N.stream_of(h.device)), "dava_bfgs_update_inverse_hessian_backward_large_f64")
+        else:
+            N.check(getattr(lib, f"dava_bfgs_update_inverse_hessian_backward_{_dt(h)}")(
+                b, n, N.ptr(h), N.ptr(s), N.ptr(y), N.ptr(grad), *outs, N.stream_of(h.device)),
+                "dava_bfgs_update_inverse_hessian_backward")
     return gh, gs, gy
 
 
@@ -1004,7 +1160,8 @@ def _(focal, cx, cy, translation, lie, world, target, visibility, minimum_z_dist
 
 
 OPS = ("bfgs_solve", "ba_solve", "ba_solve_record", "ba_solve_backward", "ba_evaluate", "ba_second_order",
-       "ba_second_order_f64", "ba_solve_record_f64", "ba_solve_backward_f64", "bfgs_update_inverse_hessian",
+       "ba_second_order_f64", "ba_solve_record_f64", "ba_solve_backward_f64", "ba_second_order_large_f64",
+       "ba_solve_record_large_f64", "ba_solve_backward_large_f64", "bfgs_update_inverse_hessian",
        "bfgs_update_inverse_hessian_backward", "bfgs_initial_scale", "bfgs_initial_scale_backward",
        "bfgs_scale_matrix", "bfgs_scale_matrix_backward", "bfgs_search_direction", "bfgs_search_direction_backward",
        "wolfe_init", "wolfe_propose", "wolfe_update", "l1_camera_evaluate", "l1_camera_vjp")

@@ -245,7 +245,11 @@ class BFGSSolver(Module):
         Differentiating through a float64 solve needs an objective built with ``float64_derivatives=True``
         (without it: ``TypeError``, second derivatives are float32 only): the recording float64 solve and its
         adjoint kernel (``dava_ba_solve_record_f64`` / ``dava_ba_solve_backward_f64``) where they apply and the
-        GENERIC_BACKWARD override is off, else the generic loop with the graph kept by torch.
+        GENERIC_BACKWARD override is off, else the generic loop with the graph kept by torch.  Beyond those kernels'
+        LDS image (160 KiB) that is a ``ValueError`` unless the objective was built with
+        ``float64_large_gradients=True``: then the recording solve and the adjoint run in their forms 1 and 2
+        (``dava_ba_solve_record_large_f64`` / ``dava_ba_solve_backward_large_f64``) at any scene size, and the
+        generic loop's graph builds on the second derivatives' large forms.
         Training mode (a drop path, ``return_second_last``) takes the same fused routes when the objective was
         built with that keyword and the GENERIC_TRAINING override is off: the seed of the counter-based schedule
         comes from torch's default generator, and a ``return_second_last`` batch in which the reference's scatter
@@ -268,7 +272,8 @@ class BFGSSolver(Module):
                  and (native_ops.solve_workspace_bytes_f64(*shape) > 0
                       or native_ops.solve_large_workspace_bytes_f64(*shape) > 0))
         one = shape[:4] + (1, fn.residual)  # (the scene alone decides: the smallest image, one iteration)
-        if (parameters.requires_grad and native_ops.solve_workspace_bytes_f64(*one) == 0
+        large = bool(getattr(fn, "float64_large_gradients", False))  # gradients beyond the LDS image (opt-in)
+        if (parameters.requires_grad and not large and native_ops.solve_workspace_bytes_f64(*one) == 0
                 and native_ops.solve_large_workspace_bytes_f64(*one) > 0):
             # beyond the LDS image there is no recording solve, no adjoint and no second derivative of the
             # objective, so the generic loop's graph could not be built either: refused here, before any launch
@@ -277,9 +282,10 @@ class BFGSSolver(Module):
                 "recording solve, its adjoint and the float64 second derivatives keep one problem's whole image in "
                 "LDS, which must fit 160 KiB; this scene solves and evaluates in float64 without a graph only")
         if parameters.requires_grad:  # the solve is a graph node only when the parameters require grad
+            supported = native_ops.solve_tape_supported_large_f64 if large else native_ops.solve_tape_supported_f64
             fused = (fused and not _native.python_knob("GENERIC_BACKWARD")
-                     and native_ops.solve_tape_supported_f64(max(x0.shape[0], 1), fn.num_views, fn.num_points,
-                                                             fn.distortion, num_iterations, fn.residual))
+                     and supported(max(x0.shape[0], 1), fn.num_views, fn.num_points, fn.distortion, num_iterations,
+                                   fn.residual))
         if fused:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0.0 else 0  # from torch's default generator
             scene = (x0, fn.observations64.reshape(-1, fn.num_views, fn.num_points, 2),
@@ -288,7 +294,7 @@ class BFGSSolver(Module):
                       error_threshold=error_threshold, iterations=num_iterations, minimum_step=self.minimum_step,
                       residual=fn.residual, drop_path_p=drop_p, drop_seed=seed, return_second_last=second_last)
             if parameters.requires_grad:
-                x, status = native_ops.ba_solve_differentiable_f64(*scene, **kw)
+                x, status = native_ops.ba_solve_differentiable_f64(*scene, large=large, **kw)
             else:
                 x, _, status = native_ops.ba_solve(*scene, hessian_mode=_native.DAVA_HESSIAN_COMPACT,
                                                    want_status=True, **kw)

@@ -51,9 +51,17 @@ _F64_FIRST_ORDER_ONLY = ("the float64 fused objectives give E and dE/dx only: se
                          "observation gradient are float32 only")
 
 
-def _second_order(x):
-    """The forward-over-reverse launch of x's dtype (float64 only on objectives built with float64_derivatives)."""
-    return native_ops.ba_second_order_f64 if x.dtype == torch.float64 else native_ops.ba_second_order
+_F64_LARGE = 2  # f64_derivatives of an objective built with float64_large_gradients=True (True / 1: without)
+
+
+def _second_order(x, f64_derivatives=False):
+    """The forward-over-reverse launch of x's dtype (float64 only on objectives built with float64_derivatives;
+    with float64_large_gradients too: the launch that takes any scene size where the LDS image does not fit)."""
+    if x.dtype != torch.float64:
+        return native_ops.ba_second_order
+    if f64_derivatives == _F64_LARGE:
+        return native_ops.ba_second_order_large_f64
+    return native_ops.ba_second_order_f64
 
 
 class _NativeObjective(torch.autograd.Function):
@@ -68,7 +76,7 @@ class _NativeObjective(torch.autograd.Function):
         if need_obs and x.dtype == torch.float64 and not f64_derivatives:
             raise TypeError(_F64_FIRST_ORDER_ONLY + " (the observations require grad)")
         if need_obs:  # dE/dobs comes from the second-order kernel (v = 0)
-            err, grad, _, obs_grad, _ = _second_order(x)(
+            err, grad, _, obs_grad, _ = _second_order(x, f64_derivatives)(
                 x, observations, visibility, num_views, num_points, distortion, residual=residual, want_hv=False)
         else:
             err, grad, _ = native_ops.ba_evaluate(x, observations, visibility, num_views, num_points, distortion,
@@ -102,10 +110,10 @@ class _NativeGradient(torch.autograd.Function):
     def forward(ctx, x, observations, visibility, num_views, num_points, distortion, residual, f64_derivatives=False):
         if x.dtype == torch.float64 and not f64_derivatives:
             raise TypeError(_F64_FIRST_ORDER_ONLY)
-        _, grad, _, obs_grad, _ = _second_order(x)(
+        _, grad, _, obs_grad, _ = _second_order(x, f64_derivatives)(
             x, observations, visibility, num_views, num_points, distortion, residual=residual, want_hv=False)
         ctx.save_for_backward(x, observations, visibility)
-        ctx.meta = (num_views, num_points, distortion, residual)
+        ctx.meta = (num_views, num_points, distortion, residual, f64_derivatives)
         ctx.set_materialize_grads(False)
         return grad, obs_grad
 
@@ -117,8 +125,9 @@ class _NativeGradient(torch.autograd.Function):
         if u is None and u_obs is None:
             return None, None, None, None, None, None, None, None
         x, obs, vis = ctx.saved_tensors
-        _, _, hv, _, obs_hv = _second_order(x)(x, obs, vis, *ctx.meta[:3], direction=u, residual=ctx.meta[3],
-                                               want_obs=ctx.needs_input_grad[1], obs_direction=u_obs)
+        _, _, hv, _, obs_hv = _second_order(x, ctx.meta[4])(x, obs, vis, *ctx.meta[:3], direction=u,
+                                                            residual=ctx.meta[3], want_obs=ctx.needs_input_grad[1],
+                                                            obs_direction=u_obs)
         return (hv if ctx.needs_input_grad[0] else None, obs_hv if ctx.needs_input_grad[1] else None,
                 None, None, None, None, None, None)
 
@@ -133,13 +142,16 @@ class ReprojectionError:
     kernels: float64 parameters then evaluate and solve in float64 (value and first derivative only;
     ``float64_derivatives=True`` -- float64 device observations required, else ``ValueError`` -- adds the float64
     second derivatives: create_graph, observations that require grad, double backward of dE/dobs, and the
-    drop-in solver differentiates through a float64 solve).  With ``distortion=True`` the
+    drop-in solver differentiates through a float64 solve; ``float64_large_gradients=True`` -- which requires
+    ``float64_derivatives=True``, else ``ValueError`` -- extends both to scenes beyond the kernels' LDS image:
+    the second derivatives, the recording solve and the adjoint in their forms 1 and 2).  With ``distortion=True`` the
     five Brown-Conrady coefficients (k1 k2 k3 p1 p2) are appended to the
     parameter vector (``camera_model/distorted_camera_model.py:59-86``).
     """
 
     def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int,
-                 distortion: bool = False, float64_derivatives: bool = False):
+                 distortion: bool = False, float64_derivatives: bool = False,
+                 float64_large_gradients: bool = False):
         if observations.shape[-3:] != (num_views, num_points, 2):
             raise ValueError(f"observations must end in ({num_views}, {num_points}, 2), got {tuple(observations.shape)}")
         if visibility.shape != observations.shape[:-1]:
@@ -158,6 +170,10 @@ class ReprojectionError:
         if self.float64_derivatives and self.observations64 is None:
             raise ValueError("float64_derivatives=True needs float64 observations on a ROCm device "
                              f"(got {observations.dtype} on {observations.device})")
+        # opt-in on top of it: second derivatives and gradients through the solve for scenes beyond the LDS image
+        self.float64_large_gradients = bool(float64_large_gradients)
+        if self.float64_large_gradients and not self.float64_derivatives:
+            raise ValueError("float64_large_gradients=True needs float64_derivatives=True")
         self.visibility = visibility.to(torch.uint8)
         self.num_views = int(num_views)
         self.num_points = int(num_points)
@@ -195,7 +211,8 @@ class ReprojectionError:
         if x.dtype not in (torch.float32, torch.float64):
             raise TypeError("ReprojectionError evaluates in float32 (or float64, built from float64 observations)")
         err = _NativeObjective.apply(x, obs, vis, self.num_views, self.num_points, self.distortion, self.residual,
-                                     self.float64_derivatives and use64)
+                                     (_F64_LARGE if self.float64_large_gradients else True)
+                                     if (self.float64_derivatives and use64) else False)
         return err.reshape(lead)
 
 
@@ -221,9 +238,9 @@ class RayAngleError(ReprojectionError):
     residual = native_ops.N.DAVA_RESIDUAL_RAY_ANGLE
 
     def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int,
-                 float64_derivatives: bool = False):
+                 float64_derivatives: bool = False, float64_large_gradients: bool = False):
         super().__init__(observations, visibility, num_views, num_points, distortion=False,
-                         float64_derivatives=float64_derivatives)
+                         float64_derivatives=float64_derivatives, float64_large_gradients=float64_large_gradients)
 
     def _torch_objective(self, x, obs, vis):
         from ..geometry.closure_ops import ray_angle_objective

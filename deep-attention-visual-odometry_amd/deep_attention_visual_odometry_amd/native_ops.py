@@ -106,6 +106,38 @@ def ba_second_order_f64(x: torch.Tensor, observations: torch.Tensor, visibility:
             obs_hv if (want_obs and want_hv) else None)
 
 
+def second_order_form_f64(batch: int, num_views: int, num_points: int, distortion: bool,
+                          residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_second_order_form_f64`` (host-only): the form the float64 second derivatives take for this scene --
+    0 the whole dual image in LDS (``dava_ba_second_order_f64``'s launch), 1 the scene read in place and the dual
+    dE/dobs in a workspace, 2 the dual x and gradient there too -- or a negative value where they do not run."""
+    from ._ops import scene_struct_f64
+
+    sc = scene_struct_f64(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
+    return int(N.load_library().dava_ba_second_order_form_f64(sc))
+
+
+def ba_second_order_large_f64(x: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
+                              num_points: int, distortion: bool = False, direction: Optional[torch.Tensor] = None,
+                              residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, want_hv: bool = True,
+                              want_obs: bool = True, obs_direction: Optional[torch.Tensor] = None):
+    """:func:`ba_second_order_f64` for a scene of any size: ``torch.ops.dava.ba_second_order_large_f64`` where
+    ``dava_ba_second_order_f64`` refuses the scene (its dual image does not fit LDS) or under the F64_FORM
+    override, else that operator itself."""
+    if second_order_form_f64(1, num_views, num_points, distortion, residual) == 0:
+        return ba_second_order_f64(x, observations, visibility, num_views, num_points, distortion, direction,
+                                   residual, want_hv, want_obs, obs_direction)
+    x = _f64_on_device(x, "x")
+    obs, vis = _scene_inputs(x, observations, visibility)
+    if obs_direction is not None:
+        obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=torch.float64)).reshape(obs.shape)
+    err, grad, hv, obs_grad, obs_hv = torch.ops.dava.ba_second_order_large_f64(
+        x, obs, vis, num_views, num_points, bool(distortion), _opt(direction, torch.float64), int(residual),
+        bool(want_hv), bool(want_obs), obs_direction)
+    return (err, grad, hv if want_hv else None, obs_grad if want_obs else None,
+            obs_hv if (want_obs and want_hv) else None)
+
+
 def ba_solve(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
              num_points: int, distortion: bool, *, sufficient_decrease: float = 1e-4, curvature: float = 0.9,
              error_threshold: float = 1e-4, iterations: int = 1000, minimum_step: float = 1e-8,
@@ -230,17 +262,48 @@ def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distor
             and int(lib.dava_ba_solve_backward_workspace_bytes_f64(sc, cfg)) > 0)
 
 
+def _f64_query(name: str, batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+               residual: int) -> int:
+    from ._ops import scene_struct_f64, solver_config_f64
+
+    sc = scene_struct_f64(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
+    cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
+    return int(getattr(N.load_library(), name)(sc, cfg))
+
+
+def solve_tape_supported_large_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+                                   residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> bool:
+    """Host-only: does this shape have the float64 fused adjoint at any scene size -- a recording forward
+    (``dava_ba_solve_tape_bytes_large_f64`` > 0) AND a backward that can launch on it
+    (``dava_ba_solve_backward_large_workspace_bytes_f64`` > 0)?"""
+    args = (batch, num_views, num_points, distortion, iterations, residual)
+    return (_f64_query("dava_ba_solve_tape_bytes_large_f64", *args) > 0
+            and _f64_query("dava_ba_solve_backward_large_workspace_bytes_f64", *args) > 0)
+
+
+def backward_form_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1000,
+                      residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_solve_backward_form_f64`` (host-only): the form the float64 adjoint takes for this scene -- 0 the
+    whole image in LDS (``dava_ba_solve_backward_f64``'s launch), 1 the scene read in place and the observation
+    cotangent accumulated in the output, 2 the 14 vectors in the workspace too -- or a negative value where it
+    does not run.  Independent of the form the recording took."""
+    return _f64_query("dava_ba_solve_backward_form_f64", batch, num_views, num_points, distortion, iterations,
+                      residual)
+
+
 class _FusedSolveF64(torch.autograd.Function):
     """:class:`_FusedSolve` in float64: the recording float64 solve (``dava_ba_solve_record_f64``) and its adjoint
-    kernel (csrc/bfgs_adjoint_f64.hip), training mode's drop path and return_second_last included.  Not
-    differentiable twice."""
+    kernel (csrc/adjoint_f64.hpp), training mode's drop path and return_second_last included.  Not
+    differentiable twice.  ``large``: the operators that take any scene size (``*_large_f64``)."""
 
     @staticmethod
-    def forward(ctx, x0, observations, visibility, num_views, num_points, distortion, residual, cfg):
+    def forward(ctx, x0, observations, visibility, num_views, num_points, distortion, residual, cfg, large=False):
         c1, c2, thr, iters, min_step, trials, strong, drop_p, drop_seed, second_last = cfg
         x0c = _f64_on_device(x0, "parameters")
         obs, vis = _scene_inputs(x0c, observations, visibility)
-        x, status, tape, _ = torch.ops.dava.ba_solve_record_f64(
+        record = torch.ops.dava.ba_solve_record_large_f64 if large else torch.ops.dava.ba_solve_record_f64
+        ctx.large = bool(large)
+        x, status, tape, _ = record(
             x0c, obs, vis, int(num_views), int(num_points), bool(distortion), float(c1), float(c2), float(thr),
             int(iters), float(min_step), int(trials), bool(strong), int(residual), False, float(drop_p),
             int(drop_seed), bool(second_last))
@@ -262,13 +325,14 @@ class _FusedSolveF64(torch.autograd.Function):
         m, n, dist, iters, residual = ctx.meta
         need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if x_grad is None:
-            return (None,) * 8
+            return (None,) * 9
         # autograd may run this backward on another stream than the recording launch's: order the
         # adjoint after the tape is written
         torch.cuda.current_stream(tape.device).wait_event(ctx.recorded)
-        gx, gobs = torch.ops.dava.ba_solve_backward_f64(_c(x_grad.to(torch.float64)), tape, status, obs, vis, m, n,
-                                                        dist, iters, residual, bool(need_obs))
-        return (gx if need_x else None, gobs if need_obs else None, None, None, None, None, None, None)
+        backward = torch.ops.dava.ba_solve_backward_large_f64 if ctx.large else torch.ops.dava.ba_solve_backward_f64
+        gx, gobs = backward(_c(x_grad.to(torch.float64)), tape, status, obs, vis, m, n, dist, iters, residual,
+                            bool(need_obs))
+        return (gx if need_x else None, gobs if need_obs else None, None, None, None, None, None, None, None)
 
 
 def ba_solve_differentiable_f64(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor,
@@ -277,13 +341,16 @@ def ba_solve_differentiable_f64(x0: torch.Tensor, observations: torch.Tensor, vi
                                 error_threshold: float = 1e-4, iterations: int = 1000, minimum_step: float = 1e-8,
                                 max_line_search_trials: int = 1000, strong: bool = True,
                                 residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, drop_path_p: float = 0.0,
-                                drop_seed: int = 0, return_second_last: bool = False):
+                                drop_seed: int = 0, return_second_last: bool = False, large: bool = False):
     """The float64 fused solve as an autograd node w.r.t. x0 and the (float64) observations, in eval mode or
     with training mode's drop path / return_second_last (as :func:`ba_solve_differentiable`).
+    ``large``: through the operators that take any scene size (``ba_solve_record_large_f64``,
+    ``ba_solve_backward_large_f64``: forms 1 and 2 beyond the LDS image, and under the F64_FORM override).
     Returns (x, status)."""
     cfg = (sufficient_decrease, curvature, error_threshold, iterations, minimum_step, max_line_search_trials, strong,
            drop_path_p, drop_seed, return_second_last)
-    return _FusedSolveF64.apply(x0, observations, visibility, num_views, num_points, distortion, residual, cfg)
+    return _FusedSolveF64.apply(x0, observations, visibility, num_views, num_points, distortion, residual, cfg,
+                                bool(large))
 
 
 def solve_workspace_bytes(batch: int, num_views: int, num_points: int, distortion: bool,

@@ -553,6 +553,70 @@ int dava_ba_evaluate_large_f64(const DavaSceneF64* scene, const double* x, const
                                const double* alpha, double* error_out, double* grad_out, double* slope_out,
                                void* stream);
 
+/* ---- float64 gradients at any scene size (additive to ABI 4) ----
+ * The recording solve, the adjoint and the second derivatives in the same three forms: 0 is the launch of the
+ * symbol without `_large`; 1 reads the scene in place; 2 also keeps the O(P) vectors in a per-problem slice of
+ * a workspace.  Every form runs one text with the same reduction trees.  No result depends on the previous
+ * contents of a tape or workspace.  The F64_FORM override raises each form as it raises the solve's.
+ *
+ * Recording: the tape layout (dava_ba_solve_tape_bytes_f64's) does not depend on the form; its history block
+ * is the solve's history workspace.  dava_ba_solve_tape_bytes_large_f64 is > 0 exactly where
+ * dava_ba_solve_large_workspace_bytes_f64 is, and equals dava_ba_solve_tape_bytes_f64 wherever that is > 0.
+ * Form 2's six vectors live in a workspace of their own: dava_ba_solve_record_large_workspace_bytes_f64 is
+ * B * 6 * Pv * 8 + 256 in form 2 and 0 in forms 0 and 1 (workspace may then be NULL).
+ * dava_ba_solve_record_large_f64 has dava_ba_solve_record_train_f64's contract (training NULL or all zero:
+ * eval mode) and, in form 0, makes its launch; x_out, error_out and status are bitwise those of
+ * dava_ba_solve_large_f64, and every tape slot the solve did not reach is zeroed. */
+size_t dava_ba_solve_tape_bytes_large_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config);
+size_t dava_ba_solve_record_large_workspace_bytes_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config);
+int dava_ba_solve_record_large_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                                   const DavaTrainingF64* training, const double* x0, double* x_out,
+                                   double* error_out, int32_t* status_out, void* tape, size_t tape_bytes,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* The adjoint.  Its form is chosen by the fit of ITS image (14 vectors of Pv doubles, the dual view constants
+ * and partials, scratch, a chunk's coefficients, and in form 0 the scene), whatever form the recording took:
+ *   0  dava_ba_solve_backward_f64's launch;
+ *   1  the vectors in LDS, the scene in place, the observation cotangent accumulated in observations_grad
+ *      (zeroed by the kernel; not formed when NULL);
+ *   2  the 14 vectors in a per-problem workspace slice too.
+ * dava_ba_solve_backward_form_f64 (host-only): 0, 1, 2, or minus the status where none runs (iterations outside
+ * 1 .. 1025, or the dual view constants alone exceed LDS).  Workspace: the rows a_j, B * K * Pv * 8, in form 2
+ * B * 14 * Pv * 8 after them, and a 256-byte tail.  dava_ba_solve_backward_large_f64 takes
+ * dava_ba_solve_backward_f64's arguments. */
+int dava_ba_solve_backward_form_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config);
+size_t dava_ba_solve_backward_large_workspace_bytes_f64(const DavaSceneF64* scene,
+                                                        const DavaSolverConfigF64* config);
+int dava_ba_solve_backward_large_f64(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const void* tape,
+                                     size_t tape_bytes, const int32_t* status, const double* x_out_grad,
+                                     double* x0_grad, double* observations_grad, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
+/* The second derivatives (dava_ba_second_order_f64's contract and outputs):
+ *   0  dava_ba_second_order_f64's launch;
+ *   1  the dual x and gradient in LDS, the scene in place, the dual dE/dobs in a workspace of B * 4MN doubles
+ *      (only when obs_grad_out or obs_hv_out is asked for);
+ *   2  the dual x and gradient in a per-problem workspace slice of 4 Pv doubles too, after the dE/dobs block.
+ * dava_ba_second_order_form_f64 (host-only): 0, 1, 2 or minus the status.  The workspace query takes whether an
+ * observation output will be asked for; it includes a 256-byte tail and is 0 only where no form runs. */
+int dava_ba_second_order_form_f64(const DavaSceneF64* scene);
+size_t dava_ba_second_order_large_workspace_bytes_f64(const DavaSceneF64* scene, int obs_outputs);
+int dava_ba_second_order_large_f64(const DavaSceneF64* scene, const double* x, const double* direction,
+                                   const double* obs_direction, double* error_out, double* grad_out, double* hv_out,
+                                   double* obs_grad_out, double* obs_hv_out, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
+/* The backward of the dense inverse-Hessian update in float64 beyond its LDS image (the generic loop's graph on a
+ * large float64 scene): dava_bfgs_update_inverse_hessian_backward_f64 keeps nine vectors of n doubles in LDS and
+ * is DAVA_ERR_UNSUPPORTED for n > 2133; this entry keeps them in a workspace of batch * 9 * n * 8 bytes and a
+ * 256-byte tail there (the query: 0 where the LDS launch is taken, which needs no workspace), the same arithmetic
+ * in the same order.  The F64_FORM override (1 | 2) asks for the workspace at any n. */
+size_t dava_bfgs_update_inverse_hessian_backward_large_workspace_bytes_f64(int64_t batch, int64_t n);
+int dava_bfgs_update_inverse_hessian_backward_large_f64(int64_t batch, int64_t n, const double* h, const double* s,
+                                                        const double* y, const double* grad_out, double* grad_h,
+                                                        double* grad_s, double* grad_y, void* workspace,
+                                                        size_t workspace_bytes, void* stream);
+
 /* ---- test and A/B hooks ----
  * The library makes its launch choices itself (LDS or global-vector mode, waves per workgroup,
  * on-chip history entries, work queue, ...) and reads NOTHING from the environment.  Tests and A/B

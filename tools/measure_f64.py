@@ -30,6 +30,19 @@ float64 and float32 fused alternated solve by solve in one process, K = 100 fixe
   m6_n700        (6 x 700, Brown-Conrady, B = 1024): float64 form 1, the form it takes, against float32.
   Every float64 run is checked: all problems finite, all took K steps.  No rate is a requirement.
 
+--mode grad --large (default output profiles/f64_large_grad.jsonl): solve PLUS gradient beyond the LDS image, the
+recording solve and the adjoint through the operators that take any scene size (dava_ba_solve_record_large_f64,
+dava_ba_solve_backward_large_f64):
+  c5             C5 (16 x 4096, B = 256, K = 20): recording and adjoint both form 2.
+  m6_n700        (6 x 700, Brown-Conrady, B = 1024, K = 100): recording form 1, adjoint form 2.
+  c3_forms       C3 (B = 8192, K = 100): the adjoint in form 0 and forced to forms 1 and 2 through F64_FORM (the
+                 recording rises with it) -- what leaving LDS costs where all three run.
+  m6_n700_b8_k20, m8_n600_b8_k20   (B = 8, K = 20) through the drop-in on an objective built with
+                 float64_large_gradients=True: the fused route against the generic float64 loop with torch's graph
+                 (GENERIC_BACKWARD).  At (6, 700) Brown-Conrady, P = 2138, the backward of the generic loop's dense
+                 update keeps its nine vectors in a workspace (past P = 2133); at (8, 600), P = 1845, in LDS.
+  The one requirement applies: the fused route beats the generic loop wherever both run.
+
 Timing: device events around each solve, every shape warmed up first, median of --repeats (>= 5) solves.
 Reported: problems/s, algorithmic HBM bytes (bench.py's compact model; 8-byte elements for float64, computed
 here), the fraction of 8 TB/s they amount to, and the ratio to the fp32 fused rate.  The one requirement
@@ -248,8 +261,65 @@ def grad_pair(tag, b, m, n, distortion, k, repeats, dev):
     return out
 
 
-def grad_vs_generic(tag, b, m, n, distortion, k, repeats, dev):
-    """Solve + backward in float64 through the drop-in: the fused route against the generic loop with torch's graph."""
+def grad_large_forms(tag, b, m, n, distortion, k, repeats, dev, forms):
+    """Solve + backward in float64 through the operators that take any scene size, in each of `forms` (None: the forms
+    the fit chooses; 1 | 2: raised through F64_FORM), alternated run by run."""
+    from deep_attention_visual_odometry_amd import _native as N
+    from deep_attention_visual_odometry_amd import native_ops
+
+    x32, obs32, vis = scene(b, m, n, distortion, dev)
+    x64, obs64 = x32.double(), obs32.double()
+    w = torch.randn(x64.shape, generator=torch.Generator().manual_seed(1), dtype=torch.float64).to(dev)
+    kw = dict(iterations=k, error_threshold=-1.0, minimum_step=-1.0)
+    marks, taken = {}, {}
+
+    def run(name, forced):
+        with N.debug_overrides(**({} if forced is None else {"F64_FORM": forced})):
+            xg, og = x64.clone().requires_grad_(True), obs64.clone().requires_grad_(True)
+            start, mid, end = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            start.record()
+            out, status = native_ops.ba_solve_differentiable_f64(xg, og, vis, m, n, distortion, large=True, **kw)
+            mid.record()
+            gx, go = torch.autograd.grad((out * w).sum(), [xg, og])
+            end.record()
+            end.synchronize()
+        finite = (torch.isfinite(gx).all(dim=-1) & (status[:, 0] == k)).float().mean().item()
+        marks[name] = (start.elapsed_time(mid) * 1e-3, mid.elapsed_time(end) * 1e-3, finite)
+
+    runs = {}
+    for forced in forms:
+        with N.debug_overrides(**({} if forced is None else {"F64_FORM": forced})):
+            rec = native_ops.solve_form_f64(b, m, n, distortion, iterations=k)
+            adj = native_ops.backward_form_f64(b, m, n, distortion, iterations=k)
+        name = f"f64_rec{rec}_adj{adj}"
+        taken[name] = (rec, adj)
+        runs[name] = (lambda name=name, forced=forced: run(name, forced))
+    for fn in runs.values():  # warm-up of every variant (module load, allocator)
+        fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in runs}
+    for _ in range(repeats):
+        for name, fn in runs.items():
+            fn()
+            times[name].append(marks[name])
+    out = {"config": "large_grad_" + tag, "batch": b, "views": m, "points": n, "distortion": distortion,
+           "iterations": k, "repeats": repeats, "device": torch.cuda.get_device_name(dev)}
+    for name in runs:
+        total = statistics.median(t[0] + t[1] for t in times[name])
+        out[name] = {"recording_form": taken[name][0], "adjoint_form": taken[name][1], "median_s": total,
+                     "recording_solve_median_s": statistics.median(t[0] for t in times[name]),
+                     "backward_median_s": statistics.median(t[1] for t in times[name]),
+                     "problems_per_s": b / total,
+                     "fraction_of_problems_with_k_steps_and_finite_gradients": times[name][-1][2]}
+    first = next(iter(runs))
+    for name in runs:
+        out[name]["rate_over_" + first] = out[name]["problems_per_s"] / out[first]["problems_per_s"]
+    return out
+
+
+def grad_vs_generic(tag, b, m, n, distortion, k, repeats, dev, large=False):
+    """Solve + backward in float64 through the drop-in: the fused route against the generic loop with torch's graph.
+    large: on an objective built with float64_large_gradients=True (a generic loop that refuses is recorded)."""
     from deep_attention_visual_odometry_amd import BFGSSolver, ReprojectionError, _native
 
     x32, obs32, vis = scene(b, m, n, distortion, dev)
@@ -260,17 +330,28 @@ def grad_vs_generic(tag, b, m, n, distortion, k, repeats, dev):
 
     def run(name):
         xg, og = x64.clone().requires_grad_(True), obs64.clone().requires_grad_(True)
-        out = solver(xg, ReprojectionError(og, vis, m, n, distortion, float64_derivatives=True))
+        out = solver(xg, ReprojectionError(og, vis, m, n, distortion, float64_derivatives=True,
+                                           float64_large_gradients=large))
         grads[name] = torch.autograd.grad((out * w).sum(), [xg, og])
         assert (solver.last_status is not None) == (name == "fused")
 
     t_fused = timed(lambda: run("fused"), repeats)
-    with _native.debug_overrides(GENERIC_BACKWARD=1):
-        t_generic = timed(lambda: run("generic"), repeats)
+    try:
+        with _native.debug_overrides(GENERIC_BACKWARD=1):
+            t_generic = timed(lambda: run("generic"), repeats)
+    except RuntimeError as e:
+        if not large:
+            raise
+        fused = statistics.median(t_fused)
+        return {"config": "large_grad_" + tag, "batch": b, "views": m, "points": n, "distortion": distortion,
+                "iterations": k, "repeats": repeats, "device": torch.cuda.get_device_name(dev),
+                "parameters": x64.shape[1], "f64_fused": {"median_s": fused, "problems_per_s": b / fused},
+                "f64_generic_graph": {"error": str(e)}, "fused_over_generic_rate": None}
     rel = [((a - c).reshape(b, -1).norm(dim=-1) / c.reshape(b, -1).norm(dim=-1)).max().item()
            for a, c in zip(grads["fused"], grads["generic"])]
     fused, generic = statistics.median(t_fused), statistics.median(t_generic)
-    return {"config": "grad_" + tag, "batch": b, "views": m, "points": n, "distortion": distortion, "iterations": k,
+    return {"config": ("large_grad_" if large else "grad_") + tag, "batch": b, "views": m, "points": n,
+            "distortion": distortion, "iterations": k,
             "repeats": repeats, "device": torch.cuda.get_device_name(dev),
             "f64_fused": {"median_s": fused, "problems_per_s": b / fused},
             "f64_generic_graph": {"median_s": generic, "problems_per_s": b / generic},
@@ -327,7 +408,8 @@ def main(argv=None):
                     help="solve: the solve alone (the default); grad: solve plus gradient; train: training mode's "
                          "drop path, solve plus gradient")
     ap.add_argument("--large", action="store_true",
-                    help="the float64 solve beyond the LDS image (forms 1 and 2) instead of --mode's runs")
+                    help="the float64 solve beyond the LDS image (forms 1 and 2) instead of --mode's runs; with "
+                         "--mode grad: solve plus gradient beyond the LDS image")
     ap.add_argument("--out", default=None,
                     help="default: profiles/f64_solve.jsonl (solve), profiles/f64_adjoint.jsonl (grad), "
                          "profiles/f64_training.jsonl (train)")
@@ -336,7 +418,11 @@ def main(argv=None):
                                                      "c3_b32_k20,c2_b1024_k100 (train)")
     args = ap.parse_args(argv)
     grad, train = args.mode == "grad", args.mode == "train"
-    if args.large:
+    large_grad = args.large and grad
+    if large_grad:
+        args.out = args.out or os.path.join(REPO, "profiles", "f64_large_grad.jsonl")
+        args.configs = args.configs or "c5,m6_n700,c3_forms,m6_n700_b8_k20,m8_n600_b8_k20"
+    elif args.large:
         grad = train = False
         args.out = args.out or os.path.join(REPO, "profiles", "f64_large.jsonl")
         args.configs = args.configs or "c5,c3_forms,m6_n700"
@@ -352,7 +438,20 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     lines, ok = [], True
     for name in args.configs.split(","):
-        if args.large and name == "c5":
+        if large_grad and name == "c5":
+            lines.append(grad_large_forms("c5", 256, 16, 4096, False, 20, args.repeats, dev, (None,)))
+        elif large_grad and name == "m6_n700":
+            lines.append(grad_large_forms("m6_n700", 1024, 6, 700, True, 100, args.repeats, dev, (None,)))
+        elif large_grad and name == "c3_forms":
+            lines.append(grad_large_forms("c3_forms", 8192, 4, 256, True, 100, args.repeats, dev, (None, 1, 2)))
+        elif large_grad and name in ("m6_n700_b8_k20", "m8_n600_b8_k20"):
+            m, n, distortion = (6, 700, True) if name.startswith("m6") else (8, 600, False)
+            line = grad_vs_generic(name, 8, m, n, distortion, 20, args.repeats, dev, large=True)
+            ok = ok and (line["fused_over_generic_rate"] is None or line["fused_over_generic_rate"] > 1.0)
+            lines.append(line)
+        elif large_grad:
+            ap.error(f"unknown configuration {name!r} for --mode grad --large")
+        elif args.large and name == "c5":
             lines.append(large_forms("large_c5", 256, 16, 4096, False, 100, args.repeats, dev, (None,)))
         elif args.large and name == "c3_forms":
             lines.append(large_forms("large_c3_forms", 8192, 4, 256, True, 100, args.repeats, dev, (None, 1, 2)))
