@@ -1,7 +1,8 @@
 // Reverse mode of the float64 fused solve: d x_out / d (x0, observations) applied to a cotangent, replaying the
-// float64 tape (dava_ba_solve_record_f64, dava_tape.hpp in doubles) backwards.  The kernel, shared by
-// bfgs_adjoint_f64.hip (form 0: dava_ba_solve_backward_f64) and bfgs_adjoint_large_f64.hip (forms 1 and 2:
-// dava_ba_solve_backward_large_f64).  As in solve_f64.hpp the body is written once and FORM, a compile-time
+// float64 tape (dava_ba_solve_record_f64, dava_tape.hpp in doubles) backwards.  The kernel, its plan (every host
+// check, once for all forms) and its launcher, shared by bfgs_adjoint_f64.hip (which instantiates form 0:
+// dava_ba_solve_backward_f64) and bfgs_adjoint_large_f64.hip (forms 1 and 2: dava_ba_solve_backward_large_f64).
+// As in solve_f64.hpp the body is written once and FORM, a compile-time
 // parameter, only says where its pointers come from:
 //   form 0  the 14 Pv vectors, the observations and visibility, and (obs_lds) the observation cotangent in LDS
 //   form 1  the 14 Pv vectors in LDS; the scene read in place; the observation cotangent accumulated in
@@ -367,19 +368,6 @@ __global__ __launch_bounds__(kBlock, 1) void bfgs_ba_adjoint_f64_kernel(adjoint_
   }
 }
 
-// DAVA_OK if the form-0 adjoint runs this scene / config (host-only); obs_lds: where the observation cotangent goes
-inline int adjoint_check(const DavaSceneF64* scene, const DavaSolverConfigF64* c, DavaScene& sc, bool& obs_lds) {
-  const int st = check_scene_f64(scene, false, sc);  // (the launch checks the data pointers itself)
-  if (st != DAVA_OK) return st;
-  if (!c || c->iterations < 0) return DAVA_ERR_INVALID_ARGUMENT;
-  if (c->iterations < 1 || c->iterations > kMaxIterations) return DAVA_ERR_UNSUPPORTED;
-  const int Pv = round_up(sc.num_parameters, 4);
-  obs_lds = carve_adjoint(sc.num_views, sc.num_points, Pv, true).total_bytes <= kMaxLdsBytes;
-  if (!obs_lds && carve_adjoint(sc.num_views, sc.num_points, Pv, false).total_bytes > kMaxLdsBytes)
-    return DAVA_ERR_UNSUPPORTED;
-  return DAVA_OK;
-}
-
 // The form the adjoint takes: the lowest whose image fits 160 KiB (form 0: with the cotangent in LDS or in the
 // output), raised (never lowered) by the F64_FORM override as choose_form (solve_f64.hpp) raises the solve's;
 // -1 where not even form 2's image (the dual view constants and partials) fits.
@@ -392,6 +380,96 @@ inline int choose_adjoint_form(int M, int N, int Pv) {
   if (form == 2 && carve_adjoint_large(M, Pv, 2).total_bytes > kMaxLdsBytes) return -1;
   return form;
 }
+
+// ---- host side (the conventions of dava_f64.hpp) ----
+struct AdjointPlan {
+  int status;
+  bool launch;  // false: return `status` (a refusal, or DAVA_OK for an empty batch)
+  int form, lds, batch, residual;
+  bool obs_lds;         // form 0: the observation cotangent accumulates in LDS (where that fits too)
+  size_t row_bytes;     // rows a_j: B x K x Pv
+  size_t vector_bytes;  // form 2: B x 14 x Pv doubles, else 0
+  TapeLayout tape;
+  LargeAdjointArgs args;  // the form-0 kernel takes its base
+  size_t workspace_bytes() const { return row_bytes + vector_bytes + kTailBytes; }  // [rows | form 2: vectors | tail]
+};
+
+// The first checks of the adjoint's entry points and all of its queries (no data pointer is looked at): what a
+// scene and a config need, from the shapes alone.
+inline AdjointPlan adjoint_shape(const DavaSceneF64* scene, const DavaSolverConfigF64* c, bool any_form) {
+  AdjointPlan p{};
+  p.form = -1;
+  DavaScene sc;
+  p.status = check_scene_f64(scene, false, sc);  // (the launch checks the data pointers itself)
+  if (p.status != DAVA_OK) return p;
+  p.status = DAVA_ERR_INVALID_ARGUMENT;
+  if (!c || c->iterations < 0) return p;
+  p.status = DAVA_ERR_UNSUPPORTED;
+  if (c->iterations < 1 || c->iterations > kMaxIterations) return p;
+  const int M = sc.num_views, N = sc.num_points, Pv = round_up(sc.num_parameters, 4);
+  const bool fits0 = carve_adjoint(M, N, Pv, false).total_bytes <= kMaxLdsBytes;
+  p.form = any_form ? choose_adjoint_form(M, N, Pv) : fits0 ? 0 : -1;
+  if (p.form < 0) return p;
+  p.status = DAVA_OK;
+  p.obs_lds = p.form == 0 && carve_adjoint(M, N, Pv, true).total_bytes <= kMaxLdsBytes;
+  p.lds = (int)(p.form == 0 ? carve_adjoint(M, N, Pv, p.obs_lds) : carve_adjoint_large(M, Pv, p.form)).total_bytes;
+  p.batch = sc.batch;
+  p.residual = sc.residual;
+  p.args.L = make_layout(&sc);
+  p.tape = tape_layout_f64(sc.batch, sc.num_parameters, c->iterations);
+  p.row_bytes = (size_t)sc.batch * p.tape.K * p.tape.Pv * sizeof(double);
+  p.vector_bytes = p.form == 2 ? (size_t)sc.batch * (kAdjVectors + 4) * p.tape.Pv * sizeof(double) : 0;
+  return p;
+}
+
+// the checks of both entry points, in their order
+inline AdjointPlan plan_adjoint(const DavaSceneF64* scene, const DavaSolverConfigF64* c, const void* tape,
+                                size_t tape_bytes, const int32_t* status, const double* x_out_grad, double* x0_grad,
+                                double* observations_grad, void* workspace, size_t workspace_bytes, bool any_form) {
+  AdjointPlan p = adjoint_shape(scene, c, any_form);
+  const auto refuse = [&p](int st) {
+    p.status = st;
+    return p;
+  };
+  if (p.status != DAVA_OK || p.batch == 0) return p;
+  if (!scene->observations || !scene->visibility || !tape || !status || !x_out_grad || !x0_grad)
+    return refuse(DAVA_ERR_INVALID_ARGUMENT);
+  const TapeLayout& tl = p.tape;
+  if (tape_bytes < tl.queue_byte) return refuse(DAVA_ERR_WORKSPACE);
+  if (!workspace || workspace_bytes < p.row_bytes + p.vector_bytes) return refuse(DAVA_ERR_WORKSPACE);  // (no tail)
+  LargeAdjointArgs& a = p.args;
+  a.Pv = tl.Pv;
+  a.K = tl.K;
+  a.tl = tl;
+  a.tape = static_cast<const double*>(tape);
+  a.obs = scene->observations;
+  a.vis = scene->visibility;
+  a.status = status;
+  a.xbar = x_out_grad;
+  a.x0_grad = x0_grad;
+  a.obs_grad = observations_grad;
+  a.arows = static_cast<double*>(workspace);
+  a.obs_lds = p.obs_lds ? 1 : 0;
+  a.vecs = p.form == 2 ? reinterpret_cast<double*>(static_cast<char*>(workspace) + p.row_bytes) : nullptr;
+  p.launch = true;
+  return p;
+}
+
+template <int FORM>
+int launch_adjoint(const AdjointPlan& p, void* stream) {
+  const adjoint_args_t<FORM>& a = p.args;
+  with_flag(p.residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+    const auto kernel = bfgs_ba_adjoint_f64_kernel<kRes, FORM>;
+    set_dynamic_lds(kernel, p.lds);
+    hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(kBlock), p.lds, static_cast<hipStream_t>(stream), a);
+  });
+  return launched();
+}
+
+// A plan's outcome where it asks for no launch, else the form-0 launch: instantiated in bfgs_adjoint_f64.hip, and
+// reached from bfgs_adjoint_large_f64.hip for a scene whose whole image fits LDS.
+int adjoint_form0(const AdjointPlan& p, void* stream);
 
 }  // namespace f64
 }  // namespace dava

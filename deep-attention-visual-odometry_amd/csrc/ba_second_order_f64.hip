@@ -12,6 +12,8 @@
 //           final barrier -- not formed when neither output is asked for
 //   form 2  as form 1, the dual x and gradient in a per-problem workspace slice of 4 Pv doubles
 // Workspace: [dual dE/dobs B x 4MN, if an observation output is asked for | form 2: B x 4 Pv | 256-byte tail].
+// The host side is one plan and one launcher for the two entry points (the conventions of dava_f64.hpp):
+// dava_ba_second_order_f64 plans with any_form = false, dava_ba_second_order_large_f64 and the queries with true.
 #include "ba_objective.hpp"
 #include "dava_debug.hpp"
 #include "dava_f64.hpp"
@@ -144,10 +146,96 @@ __global__ __launch_bounds__(kBlock, 1) void ba_second_order_f64_kernel(second_a
   }
 }
 
-template <int RES>
-static void launch_second(const SecondArgs& a, int B, int lds, hipStream_t s) {
-  set_dynamic_lds(ba_second_order_f64_kernel<RES>, lds);
-  hipLaunchKernelGGL(ba_second_order_f64_kernel<RES>, dim3(B), dim3(kBlock), lds, s, a);
+struct SecondPlan {
+  int status;
+  bool launch;  // false: return `status` (a refusal, or DAVA_OK for an empty batch)
+  int form, lds, batch, residual;
+  size_t obsd_bytes;    // forms 1 and 2 with an observation output: B x 4MN doubles, else 0
+  size_t vector_bytes;  // form 2: B x 4 Pv doubles, else 0
+  LargeSecondArgs args;  // the form-0 kernel takes its base
+  size_t workspace_bytes() const { return obsd_bytes + vector_bytes + kTailBytes; }
+};
+
+// What a scene needs, from its shape alone (obs_out: an observation output is asked for): the queries and the
+// launch's checks read the same numbers.
+inline SecondPlan second_shape(const DavaScene& sc, bool obs_out, bool any_form) {
+  SecondPlan p{};
+  const int M = sc.num_views, N = sc.num_points, Pv = round_up(sc.num_parameters, 4);
+  p.status = DAVA_ERR_UNSUPPORTED;
+  p.form = any_form ? choose_second_form(M, N, Pv) : carve_second(M, N, Pv).total_bytes <= kMaxLdsBytes ? 0 : -1;
+  if (p.form < 0) return p;
+  p.status = DAVA_OK;
+  p.lds = (int)(p.form == 0 ? carve_second(M, N, Pv) : carve_second_large(M, Pv, p.form)).total_bytes;
+  p.batch = sc.batch;
+  p.residual = sc.residual;
+  p.obsd_bytes = p.form != 0 && obs_out ? (size_t)sc.batch * 4 * M * N * sizeof(double) : 0;
+  p.vector_bytes = p.form == 2 ? (size_t)sc.batch * 4 * Pv * sizeof(double) : 0;
+  return p;
+}
+
+// the shape behind a host-only query (which looks at no data pointer)
+inline SecondPlan second_query(const DavaSceneF64* scene, bool obs_out) {
+  DavaScene sc;
+  SecondPlan p{};
+  p.form = -1;
+  p.status = check_scene_f64(scene, false, sc);
+  return p.status == DAVA_OK ? second_shape(sc, obs_out, true) : p;
+}
+
+// the checks of both entry points, in their order
+inline SecondPlan plan_second(const DavaSceneF64* scene, const double* x, const double* direction,
+                              const double* obs_direction, double* error_out, double* grad_out, double* hv_out,
+                              double* obs_grad_out, double* obs_hv_out, void* workspace, size_t workspace_bytes,
+                              bool any_form) {
+  SecondPlan p{};
+  const auto refuse = [&p](int st) {
+    p.status = st;
+    return p;
+  };
+  DavaScene sc;
+  const int st = check_scene_f64(scene, true, sc);
+  if (st != DAVA_OK) return refuse(st);
+  if (sc.batch == 0) return refuse(DAVA_OK);
+  if (!x) return refuse(DAVA_ERR_INVALID_ARGUMENT);
+  p = second_shape(sc, obs_grad_out || obs_hv_out, any_form);
+  if (p.status != DAVA_OK) return p;
+  if (p.obsd_bytes + p.vector_bytes > 0 && (!workspace || workspace_bytes < p.workspace_bytes()))
+    return refuse(DAVA_ERR_WORKSPACE);
+  LargeSecondArgs& a = p.args;
+  a.L = make_layout(&sc);
+  a.Pv = round_up(sc.num_parameters, 4);
+  a.obs = scene->observations;
+  a.vis = scene->visibility;
+  a.x = x;
+  a.v = direction;
+  a.obs_v = obs_direction;
+  a.err = error_out;
+  a.grad = grad_out;
+  a.hv = hv_out;
+  a.obs_grad = obs_grad_out;
+  a.obs_hv = obs_hv_out;
+  a.obsd = p.obsd_bytes ? static_cast<double*>(workspace) : nullptr;
+  a.vecs = p.form == 2 ? reinterpret_cast<double*>(static_cast<char*>(workspace) + p.obsd_bytes) : nullptr;
+  p.launch = true;
+  return p;
+}
+
+template <int FORM>
+int launch_second(const SecondPlan& p, void* stream) {
+  const second_args_t<FORM>& a = p.args;
+  with_flag(p.residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+    const auto kernel = ba_second_order_f64_kernel<kRes, FORM>;
+    set_dynamic_lds(kernel, p.lds);
+    hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(kBlock), p.lds, static_cast<hipStream_t>(stream), a);
+  });
+  return launched();
+}
+
+inline int run_second(const SecondPlan& p, void* stream) {
+  if (!p.launch) return p.status;
+  if (p.form == 0) return launch_second<0>(p, stream);
+  return p.form == 1 ? launch_second<1>(p, stream) : launch_second<2>(p, stream);
 }
 
 }  // namespace f64
@@ -158,113 +246,26 @@ using namespace dava;
 extern "C" int dava_ba_second_order_f64(const DavaSceneF64* scene, const double* x, const double* direction,
                                         const double* obs_direction, double* error_out, double* grad_out,
                                         double* hv_out, double* obs_grad_out, double* obs_hv_out, void* stream) {
-  DavaScene sc;
-  const int st = f64::check_scene_f64(scene, true, sc);
-  if (st != DAVA_OK) return st;
-  if (sc.batch == 0) return DAVA_OK;
-  if (!x) return DAVA_ERR_INVALID_ARGUMENT;
-  const int Pv = round_up(sc.num_parameters, 4);
-  const f64::SecondCarve cv = f64::carve_second(sc.num_views, sc.num_points, Pv);
-  if (cv.total_bytes > f64::kMaxLdsBytes) return DAVA_ERR_UNSUPPORTED;
-  f64::SecondArgs a;
-  a.L = make_layout(&sc);
-  a.Pv = Pv;
-  a.obs = scene->observations;
-  a.vis = scene->visibility;
-  a.x = x;
-  a.v = direction;
-  a.obs_v = obs_direction;
-  a.err = error_out;
-  a.grad = grad_out;
-  a.hv = hv_out;
-  a.obs_grad = obs_grad_out;
-  a.obs_hv = obs_hv_out;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int lds = (int)cv.total_bytes;
-  if (sc.residual == DAVA_RESIDUAL_RAY_ANGLE) f64::launch_second<DAVA_RESIDUAL_RAY_ANGLE>(a, sc.batch, lds, s);
-  else f64::launch_second<DAVA_RESIDUAL_SQUARED_REPROJECTION>(a, sc.batch, lds, s);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  return f64::run_second(f64::plan_second(scene, x, direction, obs_direction, error_out, grad_out, hv_out,
+                                          obs_grad_out, obs_hv_out, nullptr, 0, false), stream);
 }
-
-namespace {
-
-template <int FORM>
-void launch_second_large(const f64::LargeSecondArgs& a, int B, int lds, hipStream_t s, bool ray) {
-  auto go = [&](auto kernel) {
-    set_dynamic_lds(kernel, lds);
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(kBlock), lds, s, a);
-  };
-  if (ray) go(f64::ba_second_order_f64_kernel<DAVA_RESIDUAL_RAY_ANGLE, FORM>);
-  else go(f64::ba_second_order_f64_kernel<DAVA_RESIDUAL_SQUARED_REPROJECTION, FORM>);
-}
-
-size_t second_obsd_bytes(const DavaScene& sc) {
-  return (size_t)sc.batch * 4 * sc.num_views * sc.num_points * sizeof(double);
-}
-
-size_t second_vector_bytes(const DavaScene& sc) {
-  return (size_t)sc.batch * 4 * round_up(sc.num_parameters, 4) * sizeof(double);
-}
-
-}  // namespace
 
 // host-only: 0, 1, 2, or minus the status
 extern "C" int dava_ba_second_order_form_f64(const DavaSceneF64* scene) {
-  DavaScene sc;
-  const int st = f64::check_scene_f64(scene, false, sc);
-  if (st != DAVA_OK) return -st;
-  const int form = f64::choose_second_form(sc.num_views, sc.num_points, round_up(sc.num_parameters, 4));
-  return form < 0 ? -DAVA_ERR_UNSUPPORTED : form;
+  const f64::SecondPlan p = f64::second_query(scene, false);
+  return p.status == DAVA_OK ? p.form : -p.status;
 }
 
 // host-only; obs_outputs: an observation output (obs_grad_out or obs_hv_out) will be asked for.  0: unsupported.
 extern "C" size_t dava_ba_second_order_large_workspace_bytes_f64(const DavaSceneF64* scene, int obs_outputs) {
-  DavaScene sc;
-  if (f64::check_scene_f64(scene, false, sc) != DAVA_OK) return 0;
-  const int form = f64::choose_second_form(sc.num_views, sc.num_points, round_up(sc.num_parameters, 4));
-  if (form < 0) return 0;
-  return (form != 0 && obs_outputs ? second_obsd_bytes(sc) : 0) + (form == 2 ? second_vector_bytes(sc) : 0) +
-         f64::kTailBytes;
+  const f64::SecondPlan p = f64::second_query(scene, obs_outputs != 0);
+  return p.status == DAVA_OK ? p.workspace_bytes() : 0;
 }
 
 extern "C" int dava_ba_second_order_large_f64(const DavaSceneF64* scene, const double* x, const double* direction,
                                               const double* obs_direction, double* error_out, double* grad_out,
                                               double* hv_out, double* obs_grad_out, double* obs_hv_out,
                                               void* workspace, size_t workspace_bytes, void* stream) {
-  DavaScene sc;
-  const int st = f64::check_scene_f64(scene, true, sc);
-  if (st != DAVA_OK) return st;
-  if (sc.batch == 0) return DAVA_OK;
-  if (!x) return DAVA_ERR_INVALID_ARGUMENT;
-  const int Pv = round_up(sc.num_parameters, 4);
-  const int form = f64::choose_second_form(sc.num_views, sc.num_points, Pv);
-  if (form < 0) return DAVA_ERR_UNSUPPORTED;
-  if (form == 0)  // the whole image fits LDS: the launch of dava_ba_second_order_f64
-    return dava_ba_second_order_f64(scene, x, direction, obs_direction, error_out, grad_out, hv_out, obs_grad_out,
-                                    obs_hv_out, stream);
-  const bool obs_out = obs_grad_out || obs_hv_out;
-  const size_t obsd_bytes = obs_out ? second_obsd_bytes(sc) : 0;
-  const size_t need = obsd_bytes + (form == 2 ? second_vector_bytes(sc) : 0);
-  if (need > 0 && (!workspace || workspace_bytes < need + f64::kTailBytes)) return DAVA_ERR_WORKSPACE;
-  f64::LargeSecondArgs a;
-  a.L = make_layout(&sc);
-  a.Pv = Pv;
-  a.obs = scene->observations;
-  a.vis = scene->visibility;
-  a.x = x;
-  a.v = direction;
-  a.obs_v = obs_direction;
-  a.err = error_out;
-  a.grad = grad_out;
-  a.hv = hv_out;
-  a.obs_grad = obs_grad_out;
-  a.obs_hv = obs_hv_out;
-  a.obsd = obs_out ? static_cast<double*>(workspace) : nullptr;
-  a.vecs = form == 2 ? reinterpret_cast<double*>(static_cast<char*>(workspace) + obsd_bytes) : nullptr;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int lds = (int)f64::carve_second_large(sc.num_views, Pv, form).total_bytes;
-  const bool ray = sc.residual == DAVA_RESIDUAL_RAY_ANGLE;
-  if (form == 1) launch_second_large<1>(a, sc.batch, lds, s, ray);
-  else launch_second_large<2>(a, sc.batch, lds, s, ray);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  return f64::run_second(f64::plan_second(scene, x, direction, obs_direction, error_out, grad_out, hv_out,
+                                          obs_grad_out, obs_hv_out, workspace, workspace_bytes, true), stream);
 }

@@ -15,41 +15,9 @@
 //   dava_bfgs_search_direction_backward_*        VJP of d = -H g (:173-176)
 // Every output pointer may be NULL (that gradient is not formed).  One workgroup
 // per problem; all matrices are row-major (batch, n, n).
-#include "dava_common.hpp"
+#include "bfgs_grad_helpers.hpp"
 
 namespace dava {
-
-template <typename T>
-__device__ __forceinline__ T block_total(T v, T* red) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  v = wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// A v: one wave per row (coalesced along the row), result to out[i]
-template <typename T, typename F>
-__device__ __forceinline__ void rows_dot(int64_t n, const T* A, F&& v, T* out) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  for (int64_t i = wave; i < n; i += kWaves) {
-    T acc = 0;
-    for (int64_t j = lane; j < n; j += kWave) acc += A[i * n + j] * v(j);
-    acc = wave_sum(acc);
-    if (lane == 0) out[i] = acc;
-  }
-}
-
-// A^T u: one thread per column (consecutive threads -> consecutive columns)
-template <typename T, typename F>
-__device__ __forceinline__ void cols_dot(int64_t n, const T* A, F&& u, T* out) {
-  for (int64_t j = threadIdx.x; j < n; j += kBlock) {
-    T acc = 0;
-    for (int64_t i = 0; i < n; ++i) acc += u(i) * A[i * n + j];
-    out[j] = acc;
-  }
-}
 
 // H+ = H + (s r)(s)^T (1 + gip) - (s r)(yH)^T - (Hy)(s r)^T,  yH = y^T H, Hy = H y,
 // r = 1/(s.y) (0 if s.y <= 0), gip = yH . (y r).  Given G = dL/dH+:

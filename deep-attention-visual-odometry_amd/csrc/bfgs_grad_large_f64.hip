@@ -6,13 +6,16 @@
 // n > 2133 -- where the generic loop's graph through a float64 solve of a large scene (dense mode, the
 // GENERIC_BACKWARD override) needs it: (2, 1200) has n = 3609.  This is that kernel's text with the nine vectors in
 // a per-problem slice of a workspace, B x 9 x n doubles: the same formulas (its header comment), the same passes,
-// the same reduction trees, so the same bits where both run.  bfgs_grad.hip is shared with float32 and is left
-// as it is, hence a source of its own and copies of its three helpers.  One 256-thread workgroup per problem, which
+// the same reduction trees (the three helpers of bfgs_grad_helpers.hpp, shared with that kernel), so the same bits
+// where both run.  The two kernel bodies stay two texts: one force-inlined body taking the vectors' and the
+// reduction buffer's pointers, called from both kernels (tried with and without __restrict__ on its parameters),
+// made the compiler reschedule update_backward_kernel<float> and <double> -- 7,180 -> 7,192 bytes of code, about
+// 700 listing lines -- and that kernel is float32's too.  One 256-thread workgroup per problem, which
 // touches only its own slice and writes every vector before it reads it; __syncthreads() is the only
 // synchronisation (it orders a workgroup's global accesses as it does its LDS ones); no queue, no spin-wait.
 // Where the LDS kernel takes the shape the launch is dava_bfgs_update_inverse_hessian_backward_f64's, unless the
 // F64_FORM override (1 | 2) asks for the workspace, as it raises the forms of solve_f64.hpp.
-#include "dava_common.hpp"
+#include "bfgs_grad_helpers.hpp"
 #include "dava_debug.hpp"
 
 namespace dava {
@@ -21,37 +24,6 @@ namespace {
 constexpr int kVectors = 9;                  // yH Hy Gs GyH GTsr GTHy yHbar t1 t2
 constexpr size_t kLdsLimit = 150 * 1024;     // update_backward (bfgs_grad.hip)
 constexpr size_t kTail = 256;
-
-__device__ __forceinline__ double block_total(double v, double* red) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  v = wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// A v: one wave per row (coalesced along the row), result to out[i]
-template <typename F>
-__device__ __forceinline__ void rows_dot(int64_t n, const double* A, F&& v, double* out) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  for (int64_t i = wave; i < n; i += kWaves) {
-    double acc = 0;
-    for (int64_t j = lane; j < n; j += kWave) acc += A[i * n + j] * v(j);
-    acc = wave_sum(acc);
-    if (lane == 0) out[i] = acc;
-  }
-}
-
-// A^T u: one thread per column (consecutive threads -> consecutive columns)
-template <typename F>
-__device__ __forceinline__ void cols_dot(int64_t n, const double* A, F&& u, double* out) {
-  for (int64_t j = threadIdx.x; j < n; j += kBlock) {
-    double acc = 0;
-    for (int64_t i = 0; i < n; ++i) acc += u(i) * A[i * n + j];
-    out[j] = acc;
-  }
-}
 
 __global__ __launch_bounds__(kBlock) void update_backward_large_f64_kernel(int64_t n, const double* __restrict__ h,
                                                                            const double* __restrict__ s,

@@ -1,8 +1,10 @@
-// What the float64 sources share (bfgs_solve_f64.hip, ba_second_order_f64.hip, bfgs_adjoint_f64.hip): the
-// limits of the one-workgroup-per-problem LDS images and the host-side scene check.
+// What the float64 sources share (solve_f64.hpp, adjoint_f64.hpp, ba_second_order_f64.hip): the limits of the
+// one-workgroup-per-problem LDS images, the host-side scene check and the two helpers of their launchers.
 #pragma once
 
 #include "dava_common.hpp"
+
+#include <type_traits>
 
 namespace dava {
 namespace f64 {
@@ -20,6 +22,22 @@ inline int check_scene_f64(const DavaSceneF64* s, bool need_data, DavaScene& as3
 }
 
 inline int history_capacity(int iterations) { return iterations - 1 > 1 ? iterations - 1 : 1; }
+
+// The host side of every float64 operation is a plan and a launcher.  A plan is pure host code
+// -- no HIP call, no data pointer dereferenced -- that runs the entry point's checks in their one order and
+// leaves the status, the form, the LDS bytes, the workspace blocks and the filled kernel argument.  `any_form`
+// tells the entry points apart: false for the symbols of the LDS image (form 0 by fit alone, the F64_FORM override
+// ignored, everything else DAVA_ERR_UNSUPPORTED); true for the *_large_* symbols and the form queries, which take
+// the form choose_form / choose_adjoint_form / choose_second_form name.
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument of a launch
+template <class F>
+void with_flag(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+inline int launched() { return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH; }
 
 }  // namespace f64
 }  // namespace dava

@@ -1,5 +1,6 @@
-// The float64 kernels (objective evaluation, the one-launch BFGS + strong-Wolfe solve) and their launch plan,
-// shared by bfgs_solve_f64.hip (form 0: the whole image in LDS) and bfgs_solve_large_f64.hip (forms 1 and 2).
+// The float64 kernels (objective evaluation, the one-launch BFGS + strong-Wolfe solve) and their host side -- one
+// plan and one launcher per operation, at the end of this file -- shared by bfgs_solve_f64.hip (which instantiates
+// form 0: the whole image in LDS) and bfgs_solve_large_f64.hip (forms 1 and 2).
 // The body is written once; FORM, a compile-time parameter, only says where its pointers come from:
 //   form 0  x d g g_prev/y s H'y, the observations (as doubles) and visibility staged in LDS
 //   form 1  the six vectors in LDS, observations and visibility read in place from HBM
@@ -528,51 +529,217 @@ __global__ __launch_bounds__(kBlock, 1) void ba_evaluate_f64_kernel(EvalArgs a) 
     for (int i = tid; i < P; i += kBlock) a.grad[b * P + i] = g[i];
 }
 
-// DAVA_OK if the solve runs this scene / config (host-only)
-inline int solve_supported(const DavaScene& sc, const DavaSolverConfigF64* c) {
-  if (!c || c->iterations < 0 || c->max_line_search_trials < 0) return DAVA_ERR_INVALID_ARGUMENT;
-  if (c->iterations < 1 || c->iterations > kMaxIterations) return DAVA_ERR_UNSUPPORTED;
-  const int Pv = round_up(sc.num_parameters, 4);
-  if (carve(sc.num_views, sc.num_points, Pv, history_capacity(c->iterations)).total_bytes > kMaxLdsBytes)
-    return DAVA_ERR_UNSUPPORTED;
-  return DAVA_OK;
+// ---- host side: the solve (plain, recording, training) ----
+
+// What a scene and a config need, from the shapes alone: the size and form queries and the launch's checks read
+// the same numbers.
+struct SolveShape {
+  int status;  // DAVA_OK: `form` runs this scene / config
+  int form, Pv, kcap, lds;
+  size_t history_bytes;  // B x (S[kcap][Pv], W[kcap][Pv])
+  size_t vector_bytes;   // form 2: B x 6 x Pv doubles, else 0
+  TapeLayout tape;       // dava_tape.hpp in doubles: the layout of every form
+  // the plain solve: [history | form 2: vectors | tail]
+  size_t workspace_bytes() const { return history_bytes + vector_bytes + kTailBytes; }
+  // the recording solve, whose history is the tape's first block: [form 2: vectors | tail], else nothing
+  size_t record_workspace_bytes() const { return form == 2 ? vector_bytes + kTailBytes : 0; }
+};
+
+inline SolveShape solve_shape(const DavaScene& sc, const DavaSolverConfigF64* c, bool any_form) {
+  SolveShape s{};
+  s.form = -1;
+  s.status = DAVA_ERR_INVALID_ARGUMENT;
+  if (!c || c->iterations < 0 || c->max_line_search_trials < 0) return s;
+  s.status = DAVA_ERR_UNSUPPORTED;
+  if (c->iterations < 1 || c->iterations > kMaxIterations) return s;
+  const int M = sc.num_views, N = sc.num_points;
+  s.Pv = round_up(sc.num_parameters, 4);
+  s.kcap = history_capacity(c->iterations);
+  // (form 2's own image -- view constants, view partials, history scalars -- grows with the views: more than
+  //  251 of them at 1025 iterations do not fit)
+  s.form = any_form ? choose_form(M, N, s.Pv, s.kcap) : carve(M, N, s.Pv, s.kcap).total_bytes <= kMaxLdsBytes ? 0 : -1;
+  if (s.form < 0) return s;
+  s.status = DAVA_OK;
+  s.lds = (int)(s.form == 0 ? carve(M, N, s.Pv, s.kcap) : carve_large(M, s.Pv, s.kcap, s.form)).total_bytes;
+  s.history_bytes = (size_t)sc.batch * 2 * s.kcap * s.Pv * sizeof(double);
+  s.vector_bytes = s.form == 2 ? (size_t)sc.batch * kSolveVectors * s.Pv * sizeof(double) : 0;
+  s.tape = tape_layout_f64(sc.batch, sc.num_parameters, c->iterations);
+  return s;
 }
 
-inline size_t history_bytes(const DavaScene& sc, int iterations) {
-  return (size_t)sc.batch * 2 * history_capacity(iterations) * round_up(sc.num_parameters, 4) * sizeof(double);
+// the shape behind a host-only query (which looks at no data pointer)
+inline SolveShape solve_query(const DavaSceneF64* scene, const DavaSolverConfigF64* c, bool any_form) {
+  DavaScene sc;
+  SolveShape s{};
+  s.form = -1;
+  s.status = check_scene_f64(scene, false, sc);
+  return s.status == DAVA_OK ? solve_shape(sc, c, any_form) : s;
 }
 
-template <bool G, bool S, bool T, int FORM = 0>
-static void launch_eval(const EvalArgs& a, int B, int lds, hipStream_t s, int res) {
-  if (res == DAVA_RESIDUAL_RAY_ANGLE) {
-    const auto kernel = ba_evaluate_f64_kernel<G, S, T, DAVA_RESIDUAL_RAY_ANGLE, FORM>;
-    set_dynamic_lds(kernel, lds);
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(kBlock), lds, s, a);
-  } else {
-    const auto kernel = ba_evaluate_f64_kernel<G, S, T, DAVA_RESIDUAL_SQUARED_REPROJECTION, FORM>;
-    set_dynamic_lds(kernel, lds);
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(kBlock), lds, s, a);
+struct SolvePlan {
+  int status;
+  bool launch;  // false: return `status` (a refusal, or DAVA_OK for an empty batch)
+  bool ray, train, record;
+  SolveShape shape;
+  LargeArgs args;  // the form-0 kernels take its base, TrainArgs or SolveArgs
+};
+
+// The checks of every solve entry point, in their order.  `tape` (record): the tape, whose first block is the
+// history rows; `workspace`: the history rows and form 2's vectors, or (record) form 2's vectors alone.
+// training: null or all zero = eval mode, the instantiations without TRAIN.
+inline SolvePlan plan_solve(const DavaSceneF64* scene, const DavaSolverConfigF64* config,
+                            const DavaTrainingF64* training, const double* x0, double* x_out, double* error_out,
+                            int32_t* status_out, void* tape, size_t tape_bytes, void* workspace,
+                            size_t workspace_bytes, bool record, bool any_form) {
+  SolvePlan p{};
+  const auto refuse = [&p](int st) {
+    p.status = st;
+    return p;
+  };
+  if (training && !(training->drop_path_p >= 0.f && training->drop_path_p <= 1.f))
+    return refuse(DAVA_ERR_INVALID_ARGUMENT);
+  p.train = training && (training->drop_path_p > 0.f || training->return_second_last);
+  p.record = record;
+  DavaScene sc;
+  const int st = check_scene_f64(scene, true, sc);
+  if (st != DAVA_OK) return refuse(st);
+  const SolveShape& s = p.shape = solve_shape(sc, config, any_form);
+  if (s.status == DAVA_ERR_INVALID_ARGUMENT) return refuse(s.status);
+  if (sc.batch == 0) return refuse(DAVA_OK);
+  if (!x0 || !x_out) return refuse(DAVA_ERR_INVALID_ARGUMENT);
+  if (s.status != DAVA_OK) return refuse(s.status);
+  const int iters = config->iterations;
+  if (record) {
+    if (!status_out) return refuse(DAVA_ERR_INVALID_ARGUMENT);
+    if (!tape || tape_bytes < s.tape.total_bytes) return refuse(DAVA_ERR_WORKSPACE);
+    if (s.form == 2 && (!workspace || workspace_bytes < s.record_workspace_bytes())) return refuse(DAVA_ERR_WORKSPACE);
+  } else if ((s.form == 2 || iters > 1) && (!workspace || workspace_bytes < s.workspace_bytes())) {
+    // (the size the query reports, tail included: a queue counter put there later finds its bytes)
+    return refuse(DAVA_ERR_WORKSPACE);
   }
+  p.ray = sc.residual == DAVA_RESIDUAL_RAY_ANGLE;
+  double* tp = static_cast<double*>(tape);
+  LargeArgs& a = p.args;
+  a.L = make_layout(&sc);
+  a.B = sc.batch;
+  a.Pv = s.Pv;
+  a.kcap = s.kcap;
+  a.obs = scene->observations;
+  a.vis = scene->visibility;
+  a.x0 = x0;
+  a.x_out = x_out;
+  a.err_out = error_out;
+  a.status = status_out;
+  a.hist = record ? tp : iters > 1 ? static_cast<double*>(workspace) : nullptr;
+  a.c1 = config->sufficient_decrease;
+  a.c2 = config->curvature;
+  a.thr = config->error_threshold;
+  a.min_step = config->minimum_step;
+  a.iters = iters;
+  a.max_trials = config->max_line_search_trials;
+  a.strong = config->strong_wolfe;
+  a.tape_x = record ? tp + s.tape.x : nullptr;
+  a.tape_g = record ? tp + s.tape.g : nullptr;
+  a.tape_sc = record ? tp + s.tape.scal : nullptr;
+  a.tape_tail = record ? tp + s.tape.vecs : nullptr;
+  a.T = s.tape.T;
+  a.drop_p = p.train ? training->drop_path_p : 0.f;
+  a.drop_seed = p.train ? ((unsigned long long)training->drop_seed_hi << 32) | training->drop_seed_lo : 0ull;
+  a.second_last = p.train && training->return_second_last ? 1 : 0;
+  a.vecs = s.form != 2 ? nullptr
+           : record    ? static_cast<double*>(workspace)
+                       : reinterpret_cast<double*>(static_cast<char*>(workspace) + s.history_bytes);
+  p.launch = true;
+  return p;
 }
 
-// the instantiation for the outputs asked for (G: gradient, S: slope, T: trial point x + alpha d)
+// RES x RECORD x TRAIN of one form
 template <int FORM>
-static void launch_eval_for(const EvalArgs& a, int B, int lds, hipStream_t s, int res, bool G, bool S, bool T) {
-  if (G && S && T) launch_eval<true, true, true, FORM>(a, B, lds, s, res);
-  else if (G && S) launch_eval<true, true, false, FORM>(a, B, lds, s, res);
-  else if (G && T) launch_eval<true, false, true, FORM>(a, B, lds, s, res);
-  else if (G) launch_eval<true, false, false, FORM>(a, B, lds, s, res);
-  else if (S && T) launch_eval<false, true, true, FORM>(a, B, lds, s, res);
-  else if (S) launch_eval<false, true, false, FORM>(a, B, lds, s, res);
-  else if (T) launch_eval<false, false, true, FORM>(a, B, lds, s, res);
-  else launch_eval<false, false, false, FORM>(a, B, lds, s, res);
+int launch_solve(const SolvePlan& p, void* stream) {
+  with_flag(p.ray, [&](auto ray) {
+    with_flag(p.record, [&](auto record) {
+      with_flag(p.train, [&](auto train) {
+        constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+        constexpr bool kRecord = decltype(record)::value, kTrain = decltype(train)::value;
+        const auto kernel = bfgs_ba_solve_f64_kernel<kRes, kRecord, kTrain, FORM>;
+        const solve_args_t<kTrain, FORM>& a = p.args;  // (form 0: the base the kernel takes)
+        set_dynamic_lds(kernel, p.shape.lds);
+        hipLaunchKernelGGL(kernel, dim3(p.args.B), dim3(kBlock), p.shape.lds, static_cast<hipStream_t>(stream), a);
+      });
+    });
+  });
+  return launched();
 }
 
-// The form-0 solve behind dava_ba_solve[_train]_f64 and the recording entry points (bfgs_solve_f64.hip);
-// dava_ba_solve_large_f64 hands a scene whose whole image fits LDS to it.
-int solve_lds(const DavaSceneF64* scene, const DavaSolverConfigF64* config, const DavaTrainingF64* training,
-              const double* x0, double* x_out, double* error_out, int32_t* status_out, void* workspace,
-              size_t workspace_bytes, bool record, void* stream);
+// A plan's outcome where it asks for no launch, else the form-0 launch: instantiated in bfgs_solve_f64.hip, and
+// reached from bfgs_solve_large_f64.hip for a scene whose whole image fits LDS.
+int solve_form0(const SolvePlan& p, void* stream);
+
+// ---- host side: the evaluation ----
+struct EvalPlan {
+  int status;
+  bool launch;
+  int form, lds, batch, residual;
+  EvalArgs args;
+};
+
+inline EvalPlan plan_eval(const DavaSceneF64* scene, const double* x, const double* direction, const double* alpha,
+                          double* error_out, double* grad_out, double* slope_out, bool any_form) {
+  EvalPlan p{};
+  const auto refuse = [&p](int st) {
+    p.status = st;
+    return p;
+  };
+  DavaScene sc;
+  const int st = check_scene_f64(scene, true, sc);
+  if (st != DAVA_OK) return refuse(st);
+  if (sc.batch == 0) return refuse(DAVA_OK);
+  if (!x || !error_out) return refuse(DAVA_ERR_INVALID_ARGUMENT);
+  if (slope_out && !direction) return refuse(DAVA_ERR_INVALID_ARGUMENT);
+  const int M = sc.num_views, N = sc.num_points, Pv = round_up(sc.num_parameters, 4);
+  // (any form: more than 361 views do not fit -- form 2's view constants and partials alone)
+  p.form = any_form ? choose_form(M, N, Pv, 0) : carve(M, N, Pv, 0).total_bytes <= kMaxLdsBytes ? 0 : -1;
+  if (p.form < 0) return refuse(DAVA_ERR_UNSUPPORTED);
+  p.lds = (int)(p.form == 0 ? carve(M, N, Pv, 0) : carve_large(M, Pv, 0, p.form)).total_bytes;
+  p.batch = sc.batch;
+  p.residual = sc.residual;
+  EvalArgs& a = p.args;
+  a.L = make_layout(&sc);
+  a.Pv = Pv;
+  a.obs = scene->observations;
+  a.vis = scene->visibility;
+  a.x = x;
+  a.dir = direction;
+  a.alpha = alpha;
+  a.err = error_out;
+  a.grad = grad_out;
+  a.slope = slope_out;
+  p.launch = true;
+  return p;
+}
+
+// the instantiation for the residual and the outputs asked for (gradient, slope, trial point x + alpha d)
+template <int FORM>
+int launch_eval(const EvalPlan& p, void* stream) {
+  const EvalArgs& a = p.args;
+  with_flag(p.residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    with_flag(a.grad != nullptr, [&](auto grad) {
+      with_flag(a.slope != nullptr, [&](auto slope) {
+        with_flag(a.dir != nullptr && a.alpha != nullptr, [&](auto trial) {
+          constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+          const auto kernel = ba_evaluate_f64_kernel<decltype(grad)::value, decltype(slope)::value,
+                                                     decltype(trial)::value, kRes, FORM>;
+          set_dynamic_lds(kernel, p.lds);
+          hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(kBlock), p.lds, static_cast<hipStream_t>(stream), a);
+        });
+      });
+    });
+  });
+  return launched();
+}
+
+// as solve_form0
+int eval_form0(const EvalPlan& p, void* stream);
 
 }  // namespace f64
 }  // namespace dava

@@ -103,6 +103,14 @@ def _require_float32(x: Tensor, what: str) -> None:
                         "ba_evaluate")
 
 
+def f64_old_symbol_runs(probe) -> bool:
+    """The routing rule of every float64 operation that has a ``*_large_*`` symbol, written once: the symbol of the
+    LDS image takes the call where no F64_FORM override is set (it ignores the override, so a run that asks for
+    another form must not reach it) and ``probe()`` -- its size query, its form query or the host refusal of the
+    launch itself -- says it runs the scene; every other call goes to the ``*_large_*`` symbol."""
+    return N.library_knob("F64_FORM") <= 0 and bool(probe())
+
+
 # ---------------------------------------------------------------- fused BA ops
 
 @torch.library.custom_op("dava::ba_solve", mutates_args=("workspace",), device_types=_CUDA)
@@ -130,12 +138,11 @@ def ba_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: in
         sc64 = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
         cfg64 = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
                                   max_line_search_trials, strong)
-        # the symbols of the LDS image where it fits (and no F64_FORM override asks for another form), else the
-        # ones that take any scene size (forms 1 and 2: the scene, then the vectors too, out of LDS)
-        need = int(lib.dava_ba_solve_workspace_bytes_f64(sc64, cfg64))
-        large = need == 0 or N.library_knob("F64_FORM") > 0
-        if large:
-            need = int(lib.dava_ba_solve_large_workspace_bytes_f64(sc64, cfg64))
+        # the symbols of the LDS image where they take the call, else the ones that take any scene size (forms 1
+        # and 2: the scene, then the vectors too, out of LDS)
+        large = not f64_old_symbol_runs(lambda: lib.dava_ba_solve_workspace_bytes_f64(sc64, cfg64) > 0)
+        query = "dava_ba_solve_large_workspace_bytes_f64" if large else "dava_ba_solve_workspace_bytes_f64"
+        need = int(getattr(lib, query)(sc64, cfg64))
         if need == 0:
             raise ValueError("this scene / configuration has no float64 fused solve (1 <= iterations <= 1025, "
                              "at most 251 views at 1025 iterations)")
@@ -225,14 +232,18 @@ def ba_evaluate(x: Tensor, observations: Tensor, visibility: Tensor, num_views: 
         sc64 = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
         args = (sc64, N.ptr(x), N.ptr(direction), N.ptr(alpha), N.ptr(err), N.ptr(grad) if want_grad else None,
                 N.ptr(slope) if want_slope else None, N.stream_of(x.device))
+        status = N.DAVA_OK
+
+        def old_symbol_takes_it() -> bool:  # (its refusal comes from the host, before any launch)
+            nonlocal status
+            status = lib.dava_ba_evaluate_f64(*args)
+            return status != N.DAVA_ERR_UNSUPPORTED
+
         with torch.cuda.device(x.device):
-            # the LDS image where it fits (refused on the host, before any launch, where it does not), else --
-            # or under the F64_FORM override -- the evaluation that takes any scene size
-            st = N.DAVA_ERR_UNSUPPORTED if N.library_knob("F64_FORM") > 0 else lib.dava_ba_evaluate_f64(*args)
-            if st == N.DAVA_ERR_UNSUPPORTED:
-                N.check(lib.dava_ba_evaluate_large_f64(*args), "dava_ba_evaluate_large_f64")
+            if f64_old_symbol_runs(old_symbol_takes_it):
+                N.check(status, "dava_ba_evaluate_f64")
             else:
-                N.check(st, "dava_ba_evaluate_f64")
+                N.check(lib.dava_ba_evaluate_large_f64(*args), "dava_ba_evaluate_large_f64")
         return err, grad, slope
     sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
     with torch.cuda.device(x.device):
@@ -378,7 +389,11 @@ def _(x_out_grad, tape, status, observations, visibility, num_views, num_points,
 
 
 # ---------------------------------------- float64 second derivatives, recording solve and adjoint
-# Entry points of their own (`*_f64`): ba_second_order, ba_solve_record and ba_solve_backward stay float32 only.
+# Operators of their own: ba_second_order, ba_solve_record and ba_solve_backward stay float32 only.  Each comes as
+# a pair with one body and one fake kernel: `*_f64` keeps one problem's whole image in LDS (160 KiB), keeps its
+# limits and error texts and ignores the F64_FORM override; `*_large_f64` takes any scene size (forms 1 and 2 beyond
+# the LDS image; a scene whose image fits runs the launch of the first) and differs in the C symbols, one scratch
+# buffer and the refusal text.
 
 def _require_float64(x: Tensor, what: str) -> None:
     if x.dtype != torch.float64:
@@ -391,40 +406,67 @@ def _same_f64(t: Optional[Tensor], like: Tensor, what: str) -> None:
         raise ValueError(f"{what} must be a contiguous float64 tensor of shape {tuple(like.shape)} on {like.device}")
 
 
-@torch.library.custom_op("dava::ba_second_order_f64", mutates_args=(), device_types=_CUDA)
-def ba_second_order_f64(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                        distortion: bool, direction: Optional[Tensor], residual: int, want_hv: bool,
-                        want_obs: bool,
-                        obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """``dava_ba_second_order_f64``: ``ba_second_order`` on a float64 batch (dual numbers over double)."""
-    lib = N.load_library()
-    _require_float64(x, "the float64 second derivatives")
-    _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
-    _same_f64(direction, x, "direction")
-    _same_f64(obs_direction, observations, "obs_direction")
-    b = x.shape[0]
-    err = torch.empty(b, device=x.device, dtype=torch.float64)
-    grad = torch.empty_like(x)
-    hv = torch.empty_like(x) if want_hv else _empty0(x)
-    obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
-    obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
-    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
-    with torch.cuda.device(x.device):
-        N.check(lib.dava_ba_second_order_f64(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err),
-                                             N.ptr(grad), N.ptr(hv) if want_hv else None,
-                                             N.ptr(obs_grad) if want_obs else None,
-                                             N.ptr(obs_hv) if (want_obs and want_hv) else None, N.stream_of(x.device)),
-                "dava_ba_second_order_f64")
-    return err, grad, hv, obs_grad, obs_hv
+def _scratch(need: int, dev) -> Tensor:
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    if _POISON:  # debugging aid: every byte the kernels do not write reads back as NaN
+        ws.fill_(0xFF)
+    return ws
 
 
-@ba_second_order_f64.register_fake
-def _(x, observations, visibility, num_views, num_points, distortion, direction, residual, want_hv, want_obs,
-      obs_direction=None):
+def _second_order_f64_op(name: str, doc: str, workspace_query: Optional[str] = None, refusal: str = ""):
+    symbol = f"dava_{name}"
+
+    @torch.library.custom_op(f"dava::{name}", mutates_args=(), device_types=_CUDA)
+    def op(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int, distortion: bool,
+           direction: Optional[Tensor], residual: int, want_hv: bool, want_obs: bool,
+           obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+        lib = N.load_library()
+        _require_float64(x, "the float64 second derivatives")
+        _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
+        _same_f64(direction, x, "direction")
+        _same_f64(obs_direction, observations, "obs_direction")
+        b = x.shape[0]
+        err = torch.empty(b, device=x.device, dtype=torch.float64)
+        grad = torch.empty_like(x)
+        hv = torch.empty_like(x) if want_hv else _empty0(x)
+        obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
+        obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
+        sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+        scratch = ()
+        if workspace_query:
+            need = int(getattr(lib, workspace_query)(sc, 1 if want_obs else 0))
+            if need == 0:
+                raise ValueError(refusal)
+            ws = _scratch(need, x.device)
+            scratch = (N.ptr(ws), ws.numel())
+        with torch.cuda.device(x.device):
+            N.check(getattr(lib, symbol)(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err), N.ptr(grad),
+                                         N.ptr(hv) if want_hv else None, N.ptr(obs_grad) if want_obs else None,
+                                         N.ptr(obs_hv) if (want_obs and want_hv) else None, *scratch,
+                                         N.stream_of(x.device)), symbol)
+        return err, grad, hv, obs_grad, obs_hv
+
+    op.__doc__ = doc
+    op.register_fake(_second_order_f64_fake)
+    return op
+
+
+def _second_order_f64_fake(x, observations, visibility, num_views, num_points, distortion, direction, residual,
+                           want_hv, want_obs, obs_direction=None):
     b = x.shape[0]
     return (x.new_empty((b,)), torch.empty_like(x), torch.empty_like(x) if want_hv else x.new_empty((0,)),
             torch.empty_like(observations) if want_obs else x.new_empty((0,)),
             torch.empty_like(observations) if (want_obs and want_hv) else x.new_empty((0,)))
+
+
+ba_second_order_f64 = _second_order_f64_op(
+    "ba_second_order_f64",
+    "``dava_ba_second_order_f64``: ``ba_second_order`` on a float64 batch (dual numbers over double).")
+ba_second_order_large_f64 = _second_order_f64_op(
+    "ba_second_order_large_f64",
+    "``dava_ba_second_order_large_f64``: ``ba_second_order_f64`` for a scene of any size.",
+    "dava_ba_second_order_large_workspace_bytes_f64",
+    "this scene has no float64 second derivatives (more views than the dual view constants can hold in LDS)")
 
 
 def tape_bytes_f64(batch: int, p: int, iterations: int) -> int:
@@ -435,236 +477,130 @@ def tape_bytes_f64(batch: int, p: int, iterations: int) -> int:
     return 8 * batch * (2 * max(k - 1, 1) * pv + 2 * k * pv + (3 * k + 1 + 3) // 4 * 4) + 256
 
 
-@torch.library.custom_op("dava::ba_solve_record_f64", mutates_args=(), device_types=_CUDA)
-def ba_solve_record_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                        distortion: bool, sufficient_decrease: float, curvature: float, error_threshold: float,
-                        iterations: int, minimum_step: float, max_line_search_trials: int, strong: bool,
-                        residual: int, want_error: bool = False, drop_path_p: float = 0.0, drop_seed: int = 0,
-                        return_second_last: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+def _solve_record_f64_op(name: str, doc: str, symbol: str, tape_query: str, refusal: str,
+                         workspace_query: Optional[str] = None):
+    @torch.library.custom_op(f"dava::{name}", mutates_args=(), device_types=_CUDA)
+    def op(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int, distortion: bool,
+           sufficient_decrease: float, curvature: float, error_threshold: float, iterations: int,
+           minimum_step: float, max_line_search_trials: int, strong: bool, residual: int, want_error: bool = False,
+           drop_path_p: float = 0.0, drop_seed: int = 0,
+           return_second_last: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        lib = N.load_library()
+        _require_float64(x0, "the float64 recording solve")
+        _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
+        b, dev = x0.shape[0], x0.device
+        sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+        cfg = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
+                                max_line_search_trials, strong)
+        train = training_f64(drop_path_p, drop_seed, return_second_last)
+        need = int(getattr(lib, tape_query)(sc, cfg))
+        if need == 0:
+            raise ValueError(refusal)
+        tape = torch.empty(need, dtype=torch.uint8, device=dev)
+        if _POISON:
+            tape.fill_(0xFF)
+        scratch = ()
+        if workspace_query:  # form 2's vectors
+            ws = _scratch(int(getattr(lib, workspace_query)(sc, cfg)), dev)
+            scratch = (N.ptr(ws), ws.numel())
+        x_out = torch.empty_like(x0)
+        err = torch.empty(b, device=dev, dtype=torch.float64) if want_error else _empty0(x0)
+        status = torch.empty((b, N.STATUS_WORDS), device=dev, dtype=torch.int32)
+        with torch.cuda.device(dev):
+            N.check(getattr(lib, symbol)(sc, cfg, train, N.ptr(x0), N.ptr(x_out), N.ptr(err) if want_error else None,
+                                         N.ptr(status), N.ptr(tape), tape.numel(), *scratch, N.stream_of(dev)),
+                    symbol)
+        return x_out, status, tape, err
+
+    op.__doc__ = doc
+    op.register_fake(_solve_record_f64_fake)
+    return op
+
+
+def _solve_record_f64_fake(x0, observations, visibility, num_views, num_points, distortion, sufficient_decrease,
+                           curvature, error_threshold, iterations, minimum_step, max_line_search_trials, strong,
+                           residual, want_error=False, drop_path_p=0.0, drop_seed=0, return_second_last=False):
+    b = x0.shape[0]
+    return (torch.empty_like(x0), x0.new_empty((b, N.STATUS_WORDS), dtype=torch.int32),
+            x0.new_empty((tape_bytes_f64(b, x0.shape[1], iterations),), dtype=torch.uint8),
+            x0.new_empty((b,) if want_error else (0,)))
+
+
+ba_solve_record_f64 = _solve_record_f64_op(
+    "ba_solve_record_f64",
     """``dava_ba_solve_record_train_f64``: the float64 fused solve (bitwise ``ba_solve``'s x, error and status on a
     float64 batch, training-mode arguments included) plus the float64 tape.
-    Returns (x, status (B, 4) int32, tape uint8, error (B,) or empty)."""
-    lib = N.load_library()
-    _require_float64(x0, "the float64 recording solve")
-    _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
-    b, dev = x0.shape[0], x0.device
-    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
-    cfg = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
-                            max_line_search_trials, strong)
-    train = training_f64(drop_path_p, drop_seed, return_second_last)
-    need = int(lib.dava_ba_solve_tape_bytes_f64(sc, cfg))
-    if need == 0:
-        raise ValueError("this scene / configuration has no float64 fused solve (the LDS image must fit 160 KiB, "
-                         "1 <= iterations <= 1025)")
-    tape = torch.empty(need, dtype=torch.uint8, device=dev)
-    if _POISON:
-        tape.fill_(0xFF)
-    x_out = torch.empty_like(x0)
-    err = torch.empty(b, device=dev, dtype=torch.float64) if want_error else _empty0(x0)
-    status = torch.empty((b, N.STATUS_WORDS), device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_solve_record_train_f64(sc, cfg, train, N.ptr(x0), N.ptr(x_out),
-                                                   N.ptr(err) if want_error else None, N.ptr(status), N.ptr(tape),
-                                                   tape.numel(), N.stream_of(dev)), "dava_ba_solve_record_train_f64")
-    return x_out, status, tape, err
-
-
-@ba_solve_record_f64.register_fake
-def _(x0, observations, visibility, num_views, num_points, distortion, sufficient_decrease, curvature,
-      error_threshold, iterations, minimum_step, max_line_search_trials, strong, residual, want_error=False,
-      drop_path_p=0.0, drop_seed=0, return_second_last=False):
-    b = x0.shape[0]
-    return (torch.empty_like(x0), x0.new_empty((b, N.STATUS_WORDS), dtype=torch.int32),
-            x0.new_empty((tape_bytes_f64(b, x0.shape[1], iterations),), dtype=torch.uint8),
-            x0.new_empty((b,) if want_error else (0,)))
-
-
-@torch.library.custom_op("dava::ba_solve_backward_f64", mutates_args=(), device_types=_CUDA)
-def ba_solve_backward_f64(x_out_grad: Tensor, tape: Tensor, status: Tensor, observations: Tensor, visibility: Tensor,
-                          num_views: int, num_points: int, distortion: bool, iterations: int, residual: int,
-                          want_observations: bool) -> Tuple[Tensor, Tensor]:
-    """``dava_ba_solve_backward_f64``: (dL/dx0, dL/dobs or empty) of a recorded float64 solve for dL/dx_out."""
-    lib = N.load_library()
-    _require_float64(x_out_grad, "the float64 fused solve's adjoint")
-    _check_scene_tensors(x_out_grad, observations, visibility, num_views, num_points, distortion)
-    b, dev = x_out_grad.shape[0], x_out_grad.device
-    if tuple(status.shape) != (b, N.STATUS_WORDS) or status.dtype != torch.int32 or not status.is_contiguous():
-        raise ValueError("status must be the recording call's contiguous (B, 4) int32 tensor")
-    # the kernel dereferences tape and status as device memory of this launch: refuse anything else loudly
-    for what, t in (("tape", tape), ("status", status)):
-        if t.device != dev:
-            raise ValueError(f"{what} must be on {dev} (the cotangent's device), got {t.device}")
-    if tape.dtype != torch.uint8 or tape.dim() != 1 or not tape.is_contiguous():
-        raise ValueError("tape must be the recording call's contiguous 1-D uint8 tensor")
-    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
-    cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
-    tape_need = int(lib.dava_ba_solve_tape_bytes_f64(sc, cfg))
-    need = int(lib.dava_ba_solve_backward_workspace_bytes_f64(sc, cfg))
-    if need == 0 or tape_need == 0:
-        raise ValueError("this scene / configuration has no float64 fused adjoint")
-    if tape.numel() < tape_need:
-        raise ValueError(f"tape holds {tape.numel()} bytes; a recording of this scene and iteration count "
-                         f"writes {tape_need}")
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    if _POISON:
-        ws.fill_(0xFF)
-    gx = torch.empty_like(x_out_grad)
-    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_solve_backward_f64(sc, cfg, N.ptr(tape), tape.numel(), N.ptr(status), N.ptr(x_out_grad),
-                                               N.ptr(gx), N.ptr(gobs) if want_observations else None, N.ptr(ws),
-                                               ws.numel(), N.stream_of(dev)), "dava_ba_solve_backward_f64")
-    return gx, gobs
-
-
-@ba_solve_backward_f64.register_fake
-def _(x_out_grad, tape, status, observations, visibility, num_views, num_points, distortion, iterations, residual,
-      want_observations):
-    return (torch.empty_like(x_out_grad),
-            torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
-
-
-# ---------------------------------------- float64 gradients beyond the LDS image (forms 1 and 2)
-# Operators of their own (`*_large_f64`): the three above keep their limits and error texts, and keep ignoring the
-# F64_FORM override.  These take any scene size -- a scene whose image fits runs the launch of the symbols above.
-
-def _scratch(need: int, dev) -> Tensor:
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    if _POISON:
-        ws.fill_(0xFF)
-    return ws
-
-
-@torch.library.custom_op("dava::ba_second_order_large_f64", mutates_args=(), device_types=_CUDA)
-def ba_second_order_large_f64(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                              distortion: bool, direction: Optional[Tensor], residual: int, want_hv: bool,
-                              want_obs: bool,
-                              obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """``dava_ba_second_order_large_f64``: ``ba_second_order_f64`` for a scene of any size."""
-    lib = N.load_library()
-    _require_float64(x, "the float64 second derivatives")
-    _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
-    _same_f64(direction, x, "direction")
-    _same_f64(obs_direction, observations, "obs_direction")
-    b = x.shape[0]
-    err = torch.empty(b, device=x.device, dtype=torch.float64)
-    grad = torch.empty_like(x)
-    hv = torch.empty_like(x) if want_hv else _empty0(x)
-    obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
-    obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
-    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
-    need = int(lib.dava_ba_second_order_large_workspace_bytes_f64(sc, 1 if want_obs else 0))
-    if need == 0:
-        raise ValueError("this scene has no float64 second derivatives (more views than the dual view constants "
-                         "can hold in LDS)")
-    ws = _scratch(need, x.device)
-    with torch.cuda.device(x.device):
-        N.check(lib.dava_ba_second_order_large_f64(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err),
-                                                   N.ptr(grad), N.ptr(hv) if want_hv else None,
-                                                   N.ptr(obs_grad) if want_obs else None,
-                                                   N.ptr(obs_hv) if (want_obs and want_hv) else None, N.ptr(ws),
-                                                   ws.numel(), N.stream_of(x.device)),
-                "dava_ba_second_order_large_f64")
-    return err, grad, hv, obs_grad, obs_hv
-
-
-@ba_second_order_large_f64.register_fake
-def _(x, observations, visibility, num_views, num_points, distortion, direction, residual, want_hv, want_obs,
-      obs_direction=None):
-    b = x.shape[0]
-    return (x.new_empty((b,)), torch.empty_like(x), torch.empty_like(x) if want_hv else x.new_empty((0,)),
-            torch.empty_like(observations) if want_obs else x.new_empty((0,)),
-            torch.empty_like(observations) if (want_obs and want_hv) else x.new_empty((0,)))
-
-
-@torch.library.custom_op("dava::ba_solve_record_large_f64", mutates_args=(), device_types=_CUDA)
-def ba_solve_record_large_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                              distortion: bool, sufficient_decrease: float, curvature: float, error_threshold: float,
-                              iterations: int, minimum_step: float, max_line_search_trials: int, strong: bool,
-                              residual: int, want_error: bool = False, drop_path_p: float = 0.0, drop_seed: int = 0,
-                              return_second_last: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    Returns (x, status (B, 4) int32, tape uint8, error (B,) or empty).""",
+    "dava_ba_solve_record_train_f64", "dava_ba_solve_tape_bytes_f64",
+    "this scene / configuration has no float64 fused solve (the LDS image must fit 160 KiB, 1 <= iterations <= 1025)")
+ba_solve_record_large_f64 = _solve_record_f64_op(
+    "ba_solve_record_large_f64",
     """``dava_ba_solve_record_large_f64``: ``ba_solve_record_f64`` for a scene of any size (the same tape).
-    Returns (x, status (B, 4) int32, tape uint8, error (B,) or empty)."""
-    lib = N.load_library()
-    _require_float64(x0, "the float64 recording solve")
-    _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
-    b, dev = x0.shape[0], x0.device
-    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
-    cfg = solver_config_f64(sufficient_decrease, curvature, error_threshold, iterations, minimum_step,
-                            max_line_search_trials, strong)
-    train = training_f64(drop_path_p, drop_seed, return_second_last)
-    need = int(lib.dava_ba_solve_tape_bytes_large_f64(sc, cfg))
-    if need == 0:
-        raise ValueError("this scene / configuration has no float64 fused solve (1 <= iterations <= 1025, "
-                         "at most 251 views at 1025 iterations)")
-    tape = torch.empty(need, dtype=torch.uint8, device=dev)
-    if _POISON:
-        tape.fill_(0xFF)
-    ws = _scratch(int(lib.dava_ba_solve_record_large_workspace_bytes_f64(sc, cfg)), dev)
-    x_out = torch.empty_like(x0)
-    err = torch.empty(b, device=dev, dtype=torch.float64) if want_error else _empty0(x0)
-    status = torch.empty((b, N.STATUS_WORDS), device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_solve_record_large_f64(sc, cfg, train, N.ptr(x0), N.ptr(x_out),
-                                                   N.ptr(err) if want_error else None, N.ptr(status), N.ptr(tape),
-                                                   tape.numel(), N.ptr(ws), ws.numel(), N.stream_of(dev)),
-                "dava_ba_solve_record_large_f64")
-    return x_out, status, tape, err
+    Returns (x, status (B, 4) int32, tape uint8, error (B,) or empty).""",
+    "dava_ba_solve_record_large_f64", "dava_ba_solve_tape_bytes_large_f64",
+    "this scene / configuration has no float64 fused solve (1 <= iterations <= 1025, at most 251 views at 1025 "
+    "iterations)", "dava_ba_solve_record_large_workspace_bytes_f64")
 
 
-@ba_solve_record_large_f64.register_fake
-def _(x0, observations, visibility, num_views, num_points, distortion, sufficient_decrease, curvature,
-      error_threshold, iterations, minimum_step, max_line_search_trials, strong, residual, want_error=False,
-      drop_path_p=0.0, drop_seed=0, return_second_last=False):
-    b = x0.shape[0]
-    return (torch.empty_like(x0), x0.new_empty((b, N.STATUS_WORDS), dtype=torch.int32),
-            x0.new_empty((tape_bytes_f64(b, x0.shape[1], iterations),), dtype=torch.uint8),
-            x0.new_empty((b,) if want_error else (0,)))
+def _solve_backward_f64_op(name: str, doc: str, tape_query: str, workspace_query: str, refusal: str):
+    symbol = f"dava_{name}"
+
+    @torch.library.custom_op(f"dava::{name}", mutates_args=(), device_types=_CUDA)
+    def op(x_out_grad: Tensor, tape: Tensor, status: Tensor, observations: Tensor, visibility: Tensor,
+           num_views: int, num_points: int, distortion: bool, iterations: int, residual: int,
+           want_observations: bool) -> Tuple[Tensor, Tensor]:
+        lib = N.load_library()
+        _require_float64(x_out_grad, "the float64 fused solve's adjoint")
+        _check_scene_tensors(x_out_grad, observations, visibility, num_views, num_points, distortion)
+        b, dev = x_out_grad.shape[0], x_out_grad.device
+        if tuple(status.shape) != (b, N.STATUS_WORDS) or status.dtype != torch.int32 or not status.is_contiguous():
+            raise ValueError("status must be the recording call's contiguous (B, 4) int32 tensor")
+        # the kernel dereferences tape and status as device memory of this launch: refuse anything else loudly
+        for what, t in (("tape", tape), ("status", status)):
+            if t.device != dev:
+                raise ValueError(f"{what} must be on {dev} (the cotangent's device), got {t.device}")
+        if tape.dtype != torch.uint8 or tape.dim() != 1 or not tape.is_contiguous():
+            raise ValueError("tape must be the recording call's contiguous 1-D uint8 tensor")
+        sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
+        cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
+        tape_need = int(getattr(lib, tape_query)(sc, cfg))
+        need = int(getattr(lib, workspace_query)(sc, cfg))
+        if need == 0 or tape_need == 0:
+            raise ValueError(refusal)
+        if tape.numel() < tape_need:
+            raise ValueError(f"tape holds {tape.numel()} bytes; a recording of this scene and iteration count "
+                             f"writes {tape_need}")
+        ws = _scratch(need, dev)
+        gx = torch.empty_like(x_out_grad)
+        gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
+        with torch.cuda.device(dev):
+            N.check(getattr(lib, symbol)(sc, cfg, N.ptr(tape), tape.numel(), N.ptr(status), N.ptr(x_out_grad),
+                                         N.ptr(gx), N.ptr(gobs) if want_observations else None, N.ptr(ws), ws.numel(),
+                                         N.stream_of(dev)), symbol)
+        return gx, gobs
+
+    op.__doc__ = doc
+    op.register_fake(_solve_backward_f64_fake)
+    return op
 
 
-@torch.library.custom_op("dava::ba_solve_backward_large_f64", mutates_args=(), device_types=_CUDA)
-def ba_solve_backward_large_f64(x_out_grad: Tensor, tape: Tensor, status: Tensor, observations: Tensor,
-                                visibility: Tensor, num_views: int, num_points: int, distortion: bool,
-                                iterations: int, residual: int, want_observations: bool) -> Tuple[Tensor, Tensor]:
-    """``dava_ba_solve_backward_large_f64``: ``ba_solve_backward_f64`` for a scene of any size."""
-    lib = N.load_library()
-    _require_float64(x_out_grad, "the float64 fused solve's adjoint")
-    _check_scene_tensors(x_out_grad, observations, visibility, num_views, num_points, distortion)
-    b, dev = x_out_grad.shape[0], x_out_grad.device
-    if tuple(status.shape) != (b, N.STATUS_WORDS) or status.dtype != torch.int32 or not status.is_contiguous():
-        raise ValueError("status must be the recording call's contiguous (B, 4) int32 tensor")
-    for what, t in (("tape", tape), ("status", status)):
-        if t.device != dev:
-            raise ValueError(f"{what} must be on {dev} (the cotangent's device), got {t.device}")
-    if tape.dtype != torch.uint8 or tape.dim() != 1 or not tape.is_contiguous():
-        raise ValueError("tape must be the recording call's contiguous 1-D uint8 tensor")
-    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
-    cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
-    tape_need = int(lib.dava_ba_solve_tape_bytes_large_f64(sc, cfg))
-    need = int(lib.dava_ba_solve_backward_large_workspace_bytes_f64(sc, cfg))
-    if need == 0 or tape_need == 0:
-        raise ValueError("this scene / configuration has no float64 fused adjoint (1 <= iterations <= 1025, the "
-                         "dual view constants must fit LDS)")
-    if tape.numel() < tape_need:
-        raise ValueError(f"tape holds {tape.numel()} bytes; a recording of this scene and iteration count "
-                         f"writes {tape_need}")
-    ws = _scratch(need, dev)
-    gx = torch.empty_like(x_out_grad)
-    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_solve_backward_large_f64(sc, cfg, N.ptr(tape), tape.numel(), N.ptr(status),
-                                                     N.ptr(x_out_grad), N.ptr(gx),
-                                                     N.ptr(gobs) if want_observations else None, N.ptr(ws),
-                                                     ws.numel(), N.stream_of(dev)),
-                "dava_ba_solve_backward_large_f64")
-    return gx, gobs
-
-
-@ba_solve_backward_large_f64.register_fake
-def _(x_out_grad, tape, status, observations, visibility, num_views, num_points, distortion, iterations, residual,
-      want_observations):
+def _solve_backward_f64_fake(x_out_grad, tape, status, observations, visibility, num_views, num_points, distortion,
+                             iterations, residual, want_observations):
     return (torch.empty_like(x_out_grad),
             torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
+
+
+ba_solve_backward_f64 = _solve_backward_f64_op(
+    "ba_solve_backward_f64",
+    "``dava_ba_solve_backward_f64``: (dL/dx0, dL/dobs or empty) of a recorded float64 solve for dL/dx_out.",
+    "dava_ba_solve_tape_bytes_f64", "dava_ba_solve_backward_workspace_bytes_f64",
+    "this scene / configuration has no float64 fused adjoint")
+ba_solve_backward_large_f64 = _solve_backward_f64_op(
+    "ba_solve_backward_large_f64",
+    "``dava_ba_solve_backward_large_f64``: ``ba_solve_backward_f64`` for a scene of any size.",
+    "dava_ba_solve_tape_bytes_large_f64", "dava_ba_solve_backward_large_workspace_bytes_f64",
+    "this scene / configuration has no float64 fused adjoint (1 <= iterations <= 1025, the dual view constants must "
+    "fit LDS)")
 
 
 # ------------------------------------------------- generic BFGS building blocks

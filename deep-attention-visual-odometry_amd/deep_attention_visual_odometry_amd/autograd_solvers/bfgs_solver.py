@@ -50,6 +50,7 @@ import torch
 from torch.nn import Module
 
 from .. import _native, native_ops
+from .._ops import f64_old_symbol_runs
 from ..camera_model import ReprojectionError
 from .line_search import line_search_wolfe_conditions
 
@@ -269,8 +270,8 @@ class BFGSSolver(Module):
                                    and not (drop_p > 0.0 and _native.python_knob("GENERIC_TRAINING"))))
                  and self.hessian_mode != "dense"
                  and 1 <= num_iterations <= self.MAX_COMPACT_ENTRIES + 1
-                 and (native_ops.solve_workspace_bytes_f64(*shape) > 0
-                      or native_ops.solve_large_workspace_bytes_f64(*shape) > 0))
+                 and (f64_old_symbol_runs(lambda: native_ops.solve_workspace_bytes_f64(*shape) > 0)
+                      or native_ops.solve_large_workspace_bytes_f64(*shape) > 0))  # (ba_solve's own routing)
         one = shape[:4] + (1, fn.residual)  # (the scene alone decides: the smallest image, one iteration)
         large = bool(getattr(fn, "float64_large_gradients", False))  # gradients beyond the LDS image (opt-in)
         if (parameters.requires_grad and not large and native_ops.solve_workspace_bytes_f64(*one) == 0

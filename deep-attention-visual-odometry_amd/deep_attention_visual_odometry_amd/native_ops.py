@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _native as N
-from . import _ops  # noqa: F401  (registers torch.ops.dava.*)
+from . import _ops  # (registers torch.ops.dava.*)
 from ._ops import _dt, scene_struct, solver_config
 
 
@@ -89,21 +89,27 @@ def _f64_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
     return _c(x.detach())
 
 
+def _second_order_f64(op, x, observations, visibility, num_views, num_points, distortion, direction, residual,
+                      want_hv, want_obs, obs_direction):
+    x = _f64_on_device(x, "x")
+    obs, vis = _scene_inputs(x, observations, visibility)
+    if obs_direction is not None:
+        obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=torch.float64)).reshape(obs.shape)
+    err, grad, hv, obs_grad, obs_hv = op(
+        x, obs, vis, num_views, num_points, bool(distortion), _opt(direction, torch.float64), int(residual),
+        bool(want_hv), bool(want_obs), obs_direction)
+    return (err, grad, hv if want_hv else None, obs_grad if want_obs else None,
+            obs_hv if (want_obs and want_hv) else None)
+
+
 def ba_second_order_f64(x: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
                         num_points: int, distortion: bool = False, direction: Optional[torch.Tensor] = None,
                         residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, want_hv: bool = True,
                         want_obs: bool = True, obs_direction: Optional[torch.Tensor] = None):
     """:func:`ba_second_order` for a (B, P) float64 batch with float64 observations
     (``torch.ops.dava.ba_second_order_f64``, dual numbers over double)."""
-    x = _f64_on_device(x, "x")
-    obs, vis = _scene_inputs(x, observations, visibility)
-    if obs_direction is not None:
-        obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=torch.float64)).reshape(obs.shape)
-    err, grad, hv, obs_grad, obs_hv = torch.ops.dava.ba_second_order_f64(
-        x, obs, vis, num_views, num_points, bool(distortion), _opt(direction, torch.float64), int(residual),
-        bool(want_hv), bool(want_obs), obs_direction)
-    return (err, grad, hv if want_hv else None, obs_grad if want_obs else None,
-            obs_hv if (want_obs and want_hv) else None)
+    return _second_order_f64(torch.ops.dava.ba_second_order_f64, x, observations, visibility, num_views, num_points,
+                             distortion, direction, residual, want_hv, want_obs, obs_direction)
 
 
 def second_order_form_f64(batch: int, num_views: int, num_points: int, distortion: bool,
@@ -124,18 +130,10 @@ def ba_second_order_large_f64(x: torch.Tensor, observations: torch.Tensor, visib
     """:func:`ba_second_order_f64` for a scene of any size: ``torch.ops.dava.ba_second_order_large_f64`` where
     ``dava_ba_second_order_f64`` refuses the scene (its dual image does not fit LDS) or under the F64_FORM
     override, else that operator itself."""
-    if second_order_form_f64(1, num_views, num_points, distortion, residual) == 0:
-        return ba_second_order_f64(x, observations, visibility, num_views, num_points, distortion, direction,
-                                   residual, want_hv, want_obs, obs_direction)
-    x = _f64_on_device(x, "x")
-    obs, vis = _scene_inputs(x, observations, visibility)
-    if obs_direction is not None:
-        obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=torch.float64)).reshape(obs.shape)
-    err, grad, hv, obs_grad, obs_hv = torch.ops.dava.ba_second_order_large_f64(
-        x, obs, vis, num_views, num_points, bool(distortion), _opt(direction, torch.float64), int(residual),
-        bool(want_hv), bool(want_obs), obs_direction)
-    return (err, grad, hv if want_hv else None, obs_grad if want_obs else None,
-            obs_hv if (want_obs and want_hv) else None)
+    form0 = _ops.f64_old_symbol_runs(lambda: second_order_form_f64(1, num_views, num_points, distortion, residual) == 0)
+    op = torch.ops.dava.ba_second_order_f64 if form0 else torch.ops.dava.ba_second_order_large_f64
+    return _second_order_f64(op, x, observations, visibility, num_views, num_points, distortion, direction, residual,
+                             want_hv, want_obs, obs_direction)
 
 
 def ba_solve(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
