@@ -9,7 +9,7 @@
 // THROUGH a solve whose error function is a fused objective: autograd's double
 // backward of the reference's closure (bfgs_solver.py:133-135, create_graph)
 // becomes g's VJP = H v (+ the mixed observation term).
-#include "ba_objective.hpp"
+#include "ba_second_carve.hpp"
 
 namespace dava {
 
@@ -20,25 +20,6 @@ struct SecondArgs {
   const uint8_t* vis;
   float *err, *grad, *hv, *obs_grad, *obs_hv;
 };
-
-struct SecondCarve {
-  int x, g, views, vpart, obsd, scratch, obs, vis_bytes_off, total_bytes;  // offsets in floats
-};
-
-__host__ __device__ inline SecondCarve carve_second(int M, int N, int Pv) {
-  SecondCarve c;
-  int off = 0;
-  c.x = off; off += 2 * Pv;                                  // Dual
-  c.g = off; off += 2 * Pv;                                  // Dual
-  c.views = off; off += 2 * round_up(views_floats(M), 4);    // Dual
-  c.vpart = off; off += 2 * round_up(vpart_floats(M), 4);    // Dual
-  c.obsd = off; off += 2 * 2 * M * N;                        // Dual dE/dobs
-  c.scratch = off; off += 2 * kWaves * 32;
-  c.obs = off; off += round_up(2 * M * N, 4);
-  c.vis_bytes_off = off * 4;
-  c.total_bytes = c.vis_bytes_off + round_up(M * N, 16);
-  return c;
-}
 
 template <int RES>
 __global__ __launch_bounds__(kBlock) void ba_second_order_kernel(SecondArgs a) {

@@ -1,0 +1,74 @@
+// The geometry of the fused gradient descent (sgd_solve.hip) and of its adjoint (sgd_adjoint.hip): the LDS
+// images, the tape, and -- host only -- what the entry points and the size queries derive from
+// (scene, config).  The kernels index their LDS with the same code the host sizes it with.
+#pragma once
+
+#include "ba_second_carve.hpp"
+#include "solve_plan.hpp"
+
+namespace dava {
+
+// Forward image: x, the gradient, (LDS form) the observations, the view constants and per-wave view partials
+// of ba_eval, its reduction scratch, and (LDS form) the visibility bytes.
+struct SgdCarve {
+  int x, g, obs, views, vpart, scratch, vis_bytes_off, total_bytes;  // offsets in floats
+};
+
+__host__ __device__ inline SgdCarve carve_sgd(int M, int N, int Pv, bool gv, int nw) {
+  SgdCarve c;
+  int off = 0;
+  c.x = off; off += Pv;
+  c.g = off; off += Pv;
+  c.obs = off; off += gv ? 0 : round_up(2 * M * N, 4);
+  c.views = off; off += round_up(views_floats(M), 4);
+  c.vpart = off; off += round_up(vpart_floats(M, nw), 4);
+  c.scratch = off; off += 2 * nw * 32;
+  c.vis_bytes_off = off * 4;
+  c.total_bytes = c.vis_bytes_off + (gv ? 0 : round_up(M * N, 16));
+  return c;
+}
+
+// The tape: x_k for k = 0 .. K-1, rows of Pv = round_up(P, 4) floats, laid out (B, K, Pv).  No header.
+inline size_t sgd_tape_bytes(int B, int K, int Pv) { return (size_t)B * (size_t)K * (size_t)Pv * sizeof(float); }
+
+// Adjoint image: carve_second's (dual x and gradient, dual view constants and partials, dual dE/dobs, scratch,
+// observations, visibility) followed by the float accumulator of dL/dobs (2 M N floats).
+__host__ __device__ inline int sgd_adjoint_acc_bytes_off(const SecondCarve& c) { return c.total_bytes; }
+__host__ __device__ inline int sgd_adjoint_lds_bytes(const SecondCarve& c, int M, int N) {
+  return c.total_bytes + round_up(2 * M * N, 4) * 4;
+}
+
+// ---- host only ----
+struct SgdPlan {
+  int status;  // DAVA_OK, or why no launch runs (then the other fields are unset)
+  bool gv;     // large form
+  bool ppt;    // LDS form with a point per thread in registers
+  int Pv, lds_bytes;
+};
+
+// (a size whose images cannot be carved in 32-bit offsets is far past LDS anyway)
+inline bool sgd_sizes_sane(const DavaScene* s) {
+  return (long long)s->num_views * s->num_points <= (1 << 24) && s->num_parameters <= (1 << 24);
+}
+
+// check_scene(scene, ...) must have passed.
+inline SgdPlan plan_sgd(const DavaScene* scene, const DavaSgdConfig* config) {
+  SgdPlan p{};
+  if (!config || config->iterations < 0) {
+    p.status = DAVA_ERR_INVALID_ARGUMENT;
+    return p;
+  }
+  p.status = DAVA_ERR_UNSUPPORTED;
+  if (!sgd_sizes_sane(scene)) return p;
+  const int M = scene->num_views, N = scene->num_points;
+  p.Pv = round_up(scene->num_parameters, 4);
+  // dava_ba_evaluate's rule: the large form where the fused solve's own LDS-mode image is past its budget
+  p.gv = debug_flag(kDbgForceGV) || carve_lds(M, N, p.Pv).total_bytes > kLdsModeBudget;
+  p.ppt = !p.gv && N <= kBlock && !debug_flag(kDbgNoPPT);
+  p.lds_bytes = carve_sgd(M, N, p.Pv, p.gv, p.gv ? solve_waves(true) : kWaves).total_bytes;
+  if (p.lds_bytes > kMaxLds) return p;
+  p.status = DAVA_OK;
+  return p;
+}
+
+}  // namespace dava

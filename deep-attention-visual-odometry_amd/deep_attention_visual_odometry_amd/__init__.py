@@ -5,7 +5,7 @@ Drop-in for the hot path of jskinn/deep-attention-visual-odometry
 ``geometry/`` reprojection objective).  Compute runs in the gfx950 library
 ``_lib/libdava_ba.so`` (C ABI: include/dava_ba.h); there is no CPU path.
 """
-from .autograd_solvers import BFGSSolver, line_search_wolfe_conditions
+from .autograd_solvers import BFGSSolver, SGDSolver, line_search_wolfe_conditions
 from .camera_model import RayAngleError, ReprojectionError, num_parameters, unpack_calibration_parameters
 from .camera_model import PinholeCameraModelL1
 from .data import CameraAndParametersDataset, CameraViewsAndPoints
@@ -15,6 +15,7 @@ from .solvers import BFGSCameraSolver, IOptimisableFunction, LineSearchStrongWol
 
 __all__ = [
     "BFGSSolver",
+    "SGDSolver",
     "line_search_wolfe_conditions",
     "RayAngleError",
     "ReprojectionError",

@@ -107,6 +107,14 @@ class DavaTrainingF64(ctypes.Structure):
     ]
 
 
+class DavaSgdConfig(ctypes.Structure):
+    """The fused gradient descent (`dava_ba_sgd_*`): learning_rate is held as a float32, as the kernel uses it."""
+    _fields_ = [
+        ("learning_rate", ctypes.c_float),
+        ("iterations", _c_i32),
+    ]
+
+
 class DavaSolvePlan(ctypes.Structure):
     _fields_ = [
         ("global_vectors", _c_i32),
@@ -189,6 +197,14 @@ SIGNATURES = {
     "dava_ba_solve_backward": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSolverConfig), _vp,
                                               ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dava_ba_solve_backward_lds_entries": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSolverConfig)]),
+    # fused gradient descent (SGDSolver): solve, recording solve and adjoint (csrc/sgd_solve.hip, sgd_adjoint.hip)
+    "dava_ba_sgd_solve": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig), _vp, _vp, _vp, _vp]),
+    "dava_ba_sgd_tape_bytes": (ctypes.c_size_t, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig)]),
+    "dava_ba_sgd_solve_record": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig), _vp, _vp,
+                                                _vp, _vp, ctypes.c_size_t, _vp]),
+    "dava_ba_sgd_backward_supported": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig)]),
+    "dava_ba_sgd_backward": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig), _vp,
+                                            ctypes.c_size_t, _vp, _vp, _vp, _vp]),
     "dava_debug_set_override": (ctypes.c_int, [ctypes.c_char_p, _c_i64]),
     "dava_debug_clear_overrides": (None, []),
     "dava_abi_version": (ctypes.c_int, []),

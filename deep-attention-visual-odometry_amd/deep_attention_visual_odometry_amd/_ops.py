@@ -388,6 +388,142 @@ def _(x_out_grad, tape, status, observations, visibility, num_views, num_points,
             torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
 
 
+# ---------------------------------------- fused gradient descent (SGDSolver)
+
+def sgd_config(learning_rate: float, iterations: int) -> N.DavaSgdConfig:
+    return N.DavaSgdConfig(float(learning_rate), int(iterations))
+
+
+def sgd_tape_rows(p: int) -> int:
+    """Floats per tape row: round_up(P, 4) (csrc/sgd_plan.hpp)."""
+    return (p + 3) // 4 * 4
+
+
+def _sgd_scene(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
+               distortion: bool, learning_rate: float, iterations: int, residual: int, what: str):
+    _require_float32(x0, what)
+    _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
+    if iterations < 0:
+        raise ValueError(f"iterations must be >= 0, got {iterations}")
+    sc = scene_struct(observations, visibility, num_views, num_points, distortion, x0.shape[0], residual)
+    return sc, sgd_config(learning_rate, iterations)
+
+
+_SGD_REFUSAL = ("this scene has no fused gradient descent: its image (x and the gradient, 2 round_up(P, 4) floats, "
+                "and the objective's view constants) does not fit one workgroup's 160 KiB of LDS")
+
+
+@torch.library.custom_op("dava::ba_sgd_solve", mutates_args=(), device_types=_CUDA)
+def ba_sgd_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
+                 distortion: bool, learning_rate: float, iterations: int, residual: int,
+                 want_errors: bool) -> Tuple[Tensor, Tensor]:
+    """``dava_ba_sgd_solve``: ``iterations`` steps x <- x - learning_rate dE/dx of a (B, P) fp32 batch in one
+    launch.  Returns (x, E(x_k) (B, iterations) or empty)."""
+    lib = N.load_library()
+    sc, cfg = _sgd_scene(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+                         residual, "the fused gradient descent")
+    b, dev = x0.shape[0], x0.device
+    x_out = torch.empty_like(x0)
+    errs = torch.empty((b, iterations), device=dev, dtype=torch.float32) if want_errors else _empty0(x0)
+    with torch.cuda.device(dev):
+        status = lib.dava_ba_sgd_solve(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
+                                       N.stream_of(dev))
+    if status == N.DAVA_ERR_UNSUPPORTED:
+        raise ValueError(_SGD_REFUSAL)
+    N.check(status, "dava_ba_sgd_solve")
+    return x_out, errs
+
+
+@ba_sgd_solve.register_fake
+def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
+      want_errors):
+    return torch.empty_like(x0), x0.new_empty((x0.shape[0], iterations) if want_errors else (0,))
+
+
+@torch.library.custom_op("dava::ba_sgd_solve_differentiable", mutates_args=(), device_types=_CUDA)
+def ba_sgd_solve_differentiable(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
+                                num_points: int, distortion: bool, learning_rate: float, iterations: int,
+                                residual: int, want_errors: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """``dava_ba_sgd_solve_record``: ``ba_sgd_solve`` (bitwise its x and errors) that also writes the tape
+    (B, iterations, round_up(P, 4)) of x_k.  An autograd node w.r.t. x0 and the observations: its backward is
+    ``ba_sgd_backward`` (not differentiable twice).  Returns (x, errors or empty, tape)."""
+    lib = N.load_library()
+    sc, cfg = _sgd_scene(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+                         residual, "the recording gradient descent")
+    if not lib.dava_ba_sgd_backward_supported(sc, cfg):
+        raise ValueError("this scene has no fused adjoint of the gradient descent: its dual-number image must fit "
+                         "one workgroup's 160 KiB of LDS")
+    b, dev = x0.shape[0], x0.device
+    tape = torch.empty((b, iterations, sgd_tape_rows(x0.shape[1])), device=dev, dtype=torch.float32)
+    if _POISON:
+        tape.fill_(float("nan"))
+    x_out = torch.empty_like(x0)
+    errs = torch.empty((b, iterations), device=dev, dtype=torch.float32) if want_errors else _empty0(x0)
+    with torch.cuda.device(dev):
+        N.check(lib.dava_ba_sgd_solve_record(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
+                                             N.ptr(tape) if tape.numel() else None, tape.numel() * 4,
+                                             N.stream_of(dev)), "dava_ba_sgd_solve_record")
+    return x_out, errs, tape
+
+
+@ba_sgd_solve_differentiable.register_fake
+def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
+      want_errors):
+    b = x0.shape[0]
+    return (torch.empty_like(x0), x0.new_empty((b, iterations) if want_errors else (0,)),
+            x0.new_empty((b, iterations, sgd_tape_rows(x0.shape[1]))))
+
+
+@torch.library.custom_op("dava::ba_sgd_backward", mutates_args=(), device_types=_CUDA)
+def ba_sgd_backward(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
+                    num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int,
+                    want_observations: bool) -> Tuple[Tensor, Tensor]:
+    """``dava_ba_sgd_backward``: (dL/dx0, dL/dobs or empty) of a recorded descent for dL/dx_out."""
+    lib = N.load_library()
+    sc, cfg = _sgd_scene(x_out_grad, observations, visibility, num_views, num_points, distortion, learning_rate,
+                         iterations, residual, "the gradient descent's adjoint")
+    b, dev = x_out_grad.shape[0], x_out_grad.device
+    # the kernel dereferences the tape as device memory of this launch: refuse anything else loudly
+    if (tape.device != dev or tape.dtype != torch.float32 or not tape.is_contiguous()
+            or tuple(tape.shape) != (b, iterations, sgd_tape_rows(x_out_grad.shape[1]))):
+        raise ValueError(f"tape must be the recording call's contiguous float32 ({b}, {iterations}, "
+                         f"{sgd_tape_rows(x_out_grad.shape[1])}) tensor on {dev}, got {tuple(tape.shape)} "
+                         f"{tape.dtype} on {tape.device}")
+    gx = torch.empty_like(x_out_grad)
+    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
+    with torch.cuda.device(dev):
+        N.check(lib.dava_ba_sgd_backward(sc, cfg, N.ptr(tape) if tape.numel() else None, tape.numel() * 4,
+                                         N.ptr(x_out_grad), N.ptr(gx), N.ptr(gobs) if want_observations else None,
+                                         N.stream_of(dev)), "dava_ba_sgd_backward")
+    return gx, gobs
+
+
+@ba_sgd_backward.register_fake
+def _(x_out_grad, tape, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+      residual, want_observations):
+    return (torch.empty_like(x_out_grad),
+            torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
+
+
+def _sgd_setup_context(ctx, inputs, output):
+    x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual, _ = inputs
+    ctx.save_for_backward(output[2], observations, visibility)
+    ctx.meta = (num_views, num_points, distortion, learning_rate, iterations, residual)
+
+
+@torch.autograd.function.once_differentiable
+def _sgd_backward(ctx, x_grad, _errors_grad, _tape_grad):
+    tape, observations, visibility = ctx.saved_tensors
+    need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    x_grad = x_grad.to(torch.float32)
+    gx, gobs = ba_sgd_backward(x_grad if x_grad.is_contiguous() else x_grad.contiguous(), tape, observations.detach(),
+                               visibility, *ctx.meta, bool(need_obs))
+    return (gx if need_x else None, gobs if need_obs else None) + (None,) * 8
+
+
+ba_sgd_solve_differentiable.register_autograd(_sgd_backward, setup_context=_sgd_setup_context)
+
+
 # ---------------------------------------- float64 second derivatives, recording solve and adjoint
 # Operators of their own: ba_second_order, ba_solve_record and ba_solve_backward stay float32 only.  Each comes as
 # a pair with one body and one fake kernel: `*_f64` keeps one problem's whole image in LDS (160 KiB), keeps its
@@ -1100,4 +1236,5 @@ OPS = ("bfgs_solve", "ba_solve", "ba_solve_record", "ba_solve_backward", "ba_eva
        "ba_solve_record_large_f64", "ba_solve_backward_large_f64", "bfgs_update_inverse_hessian",
        "bfgs_update_inverse_hessian_backward", "bfgs_initial_scale", "bfgs_initial_scale_backward",
        "bfgs_scale_matrix", "bfgs_scale_matrix_backward", "bfgs_search_direction", "bfgs_search_direction_backward",
-       "wolfe_init", "wolfe_propose", "wolfe_update", "l1_camera_evaluate", "l1_camera_vjp")
+       "wolfe_init", "wolfe_propose", "wolfe_update", "l1_camera_evaluate", "l1_camera_vjp",
+       "ba_sgd_solve", "ba_sgd_solve_differentiable", "ba_sgd_backward")

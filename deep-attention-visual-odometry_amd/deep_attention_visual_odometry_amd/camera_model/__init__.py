@@ -10,7 +10,7 @@ whose value and derivatives (first order, and second order for
 create_graph callers: H v and the observation cross term) come from HIP
 kernels, differentiable w.r.t. the parameters and the observations.
 """
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -189,7 +189,9 @@ class ReprojectionError:
     def batch_shape(self) -> torch.Size:
         return self.observations.shape[:-3]
 
-    def __call__(self, parameters: torch.Tensor, batch_mask: torch.Tensor) -> torch.Tensor:
+    def __call__(self, parameters: torch.Tensor, batch_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``batch_mask`` None means every problem: the one-argument contract of ``SGDSolver``'s error function
+        (``autograd_solvers/sgd_solver.py:29``)."""
         if parameters.size(-1) != self.num_parameters:
             raise ValueError(f"expected {self.num_parameters} parameters, got {parameters.size(-1)}")
         on_device = parameters.device.type != "cpu"
@@ -197,8 +199,10 @@ class ReprojectionError:
             raise TypeError("ReprojectionError evaluates in float32 (construct it from float64 observations to "
                             "evaluate float64 parameters)")
         use64 = on_device and parameters.dtype == torch.float64
-        obs = (self.observations64 if use64 else self.observations)[batch_mask]
-        vis = self.visibility[batch_mask]
+        obs = self.observations64 if use64 else self.observations
+        vis = self.visibility
+        if batch_mask is not None:
+            obs, vis = obs[batch_mask], vis[batch_mask]
         lead = parameters.shape[:-1]
         x = parameters.reshape(-1, parameters.size(-1))
         obs = obs.reshape(-1, self.num_views, self.num_points, 2)

@@ -246,6 +246,63 @@ def ba_solve_differentiable(x0: torch.Tensor, observations: torch.Tensor, visibi
     return _FusedSolve.apply(x0, observations, visibility, num_views, num_points, distortion, residual, cfg)
 
 
+def _sgd_query(name: str, batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+               residual: int) -> int:
+    sc = scene_struct(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
+    return int(getattr(N.load_library(), name)(sc, _ops.sgd_config(0.0, iterations)))
+
+
+def sgd_tape_bytes(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+                   residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_sgd_tape_bytes`` (host-only): B * iterations * round_up(P, 4) * 4, or 0 where the fused gradient
+    descent does not run this scene (and for ``iterations == 0``, which needs no tape)."""
+    return _sgd_query("dava_ba_sgd_tape_bytes", batch, num_views, num_points, distortion, iterations, residual)
+
+
+def sgd_solve_supported(batch: int, num_views: int, num_points: int, distortion: bool,
+                        residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> bool:
+    """Host-only: does the fused gradient descent run this scene (one of its two LDS images fits)?"""
+    return sgd_tape_bytes(batch, num_views, num_points, distortion, 1, residual) > 0
+
+
+def sgd_backward_supported(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+                           residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> bool:
+    """``dava_ba_sgd_backward_supported`` (host-only): does the descent's adjoint kernel run this scene?"""
+    return _sgd_query("dava_ba_sgd_backward_supported", batch, num_views, num_points, distortion, iterations,
+                      residual) > 0
+
+
+def ba_sgd_solve(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
+                 num_points: int, distortion: bool, *, learning_rate: float, iterations: int,
+                 residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, want_errors: bool = False):
+    """``iterations`` steps of x <- x - learning_rate dE/dx for a (B, P) fp32 batch in one launch
+    (``torch.ops.dava.ba_sgd_solve``).  Returns (x, E(x_k) (B, iterations) | None).  No graph."""
+    x0 = _fp32_on_device(x0, "parameters")
+    obs, vis = _scene_inputs(x0, observations, visibility)
+    x, errs = torch.ops.dava.ba_sgd_solve(x0, obs, vis, int(num_views), int(num_points), bool(distortion),
+                                          float(learning_rate), int(iterations), int(residual), bool(want_errors))
+    return x, (errs if want_errors else None)
+
+
+def ba_sgd_solve_differentiable(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor,
+                                num_views: int, num_points: int, distortion: bool, *, learning_rate: float,
+                                iterations: int, residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION,
+                                want_errors: bool = False):
+    """The fused gradient descent as an autograd node w.r.t. x0 and the observations: the recording launch, and
+    the adjoint kernel as its backward (``torch.ops.dava.ba_sgd_solve_differentiable``).  Returns (x, errors |
+    None); the errors carry no graph."""
+    N.require_device_tensor(x0, "parameters")
+    if x0.dtype != torch.float32:
+        raise TypeError("the fused BA kernels compute in float32 (the reference's BA dtype)")
+    dev = x0.device
+    obs = _c(observations.to(device=dev, dtype=torch.float32))  # (kept in the graph)
+    vis = _c(visibility.detach().to(device=dev, dtype=torch.uint8))
+    x, errs, _ = torch.ops.dava.ba_sgd_solve_differentiable(
+        _c(x0), obs, vis, int(num_views), int(num_points), bool(distortion), float(learning_rate), int(iterations),
+        int(residual), bool(want_errors))
+    return x, (errs.detach() if want_errors else None)
+
+
 def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
                              residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> bool:
     """Host-only: does this shape have the float64 fused adjoint -- a recording forward

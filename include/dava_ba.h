@@ -331,6 +331,48 @@ int dava_ba_second_order_obs(const DavaScene* scene, const float* x, const float
                              float* error_out, float* grad_out, float* hv_out, float* obs_grad_out, float* obs_hv_out,
                              void* stream);
 
+/* ---- fused gradient descent (additive to ABI 4) ----
+ * Replaces SGDSolver.forward(parameters, error_function) (autograd_solvers/sgd_solver.py:29-44) with
+ * error_function = the objective over `scene`:
+ *   for k in 0 .. iterations-1:  x_{k+1} = x_k - learning_rate * dE/dx(x_k)
+ * fp32; the update rounds the product, then the difference, as torch does.  No stopping rule, no mask.  One
+ * launch, one workgroup per problem: the scene, x and the gradient in LDS (C1-C3), or x and the gradient in
+ * LDS and the scene read in place (C5).  A scene whose image fits neither form: DAVA_ERR_UNSUPPORTED, and 0
+ * from the size query.  iterations == 0 copies x0.  The FORCE_GV override asks for the second form. */
+typedef struct DavaSgdConfig {
+  float learning_rate;
+  int32_t iterations; /* K >= 0 */
+} DavaSgdConfig;
+
+/*   x0 (B, P), x_out (B, P) (may alias x0), error_trace_out (B, K) E(x_k) for k = 0 .. K-1, or NULL */
+int dava_ba_sgd_solve(const DavaScene* scene, const DavaSgdConfig* config, const float* x0, float* x_out,
+                      float* error_trace_out, void* stream);
+
+/* Bytes of the tape of a recording solve: x_k for k = 0 .. K-1 in rows of Pv = round_up(P, 4) floats, laid out
+ * (B, K, Pv), no header: B * K * Pv * 4.  0 if the scene / config is invalid or unsupported (and for K = 0,
+ * where no tape is needed and `tape` may be NULL). */
+size_t dava_ba_sgd_tape_bytes(const DavaScene* scene, const DavaSgdConfig* config);
+
+/* dava_ba_sgd_solve (bitwise the same x_out and error trace) that also writes the tape.  A tape below the
+ * query's figure: DAVA_ERR_WORKSPACE. */
+int dava_ba_sgd_solve_record(const DavaScene* scene, const DavaSgdConfig* config, const float* x0, float* x_out,
+                             float* error_trace_out, void* tape, size_t tape_bytes, void* stream);
+
+/* Host-only: 1 where dava_ba_sgd_backward runs this scene / config, else 0.  Its LDS image is the second
+ * derivatives' dual image (dava_ba_second_order) plus a float accumulator for dL/dobs, and must fit 160 KiB
+ * (C1-C3 do; C5 does not). */
+int dava_ba_sgd_backward_supported(const DavaScene* scene, const DavaSgdConfig* config);
+
+/* Vector-Jacobian product of the recorded descent: given x_out_grad = dL/dx_K (B, P), writes
+ *   x0_grad            (B, P)        dL/dx_0
+ *   observations_grad  (B, M, N, 2)  dL/dobs (or NULL: not formed; x0_grad is bitwise the same)
+ * replaying the tape backwards with one dual-number pass of the objective per step:
+ *   lambda <- lambda - lr H(x_k) lambda,  dL/dobs <- dL/dobs - lr (d2E/dobs dx)(x_k) lambda.
+ * scene / config must be those of the recording call, the tape unmodified.  One workgroup per problem,
+ * deterministic.  DAVA_ERR_UNSUPPORTED where dava_ba_sgd_backward_supported is 0. */
+int dava_ba_sgd_backward(const DavaScene* scene, const DavaSgdConfig* config, const void* tape, size_t tape_bytes,
+                         const float* x_out_grad, float* x0_grad, float* observations_grad, void* stream);
+
 /* ---- generic BFGS building blocks (drive an arbitrary error closure) ----
  * batch = number of problems (all leading dims flattened), n = P.          */
 

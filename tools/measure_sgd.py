@@ -1,0 +1,132 @@
+"""The fused gradient descent (SGDSolver on a fused objective) against the same work composed from the operators
+the package had before it, one JSON line per configuration (default: profiles/sgd_solve.jsonl).
+
+  fused_forward      dava_ba_sgd_solve: K steps in one launch
+  composed_forward   K x dava_ba_evaluate (value + gradient) with the torch update x <- x - lr g between them
+  fused_gradient     the recording launch + the adjoint kernel: x_K, then d (w . x_K) / d x0 and / d obs
+  composed_gradient  the torch loop over ReprojectionError with create_graph (the objective's double backward is
+                     dava_ba_second_order), then the same backward
+
+Configurations: C2 (2 x 128, B = 1024) and C3 (4 x 256 + Brown-Conrady, B = 8192), K = 100, lr = 1e-4.  The two
+paths of a pair run interleaved in one process, in both orders, best of `--repeats` (>= 5) rounds after a warm-up;
+times are HIP events around the calls, ended by a device synchronise.  For C3 the line also gives the ratio of
+the fused forward to K x 108.04 us, the time of one C3 evaluation sweep alone at B = 8192
+(profiles/r05_eval_summary.json).  Needs a ROCm device: there is no fallback.
+
+usage: python tools/measure_sgd.py [--out FILE] [--repeats 5] [--configs c2:1024,c3:8192] [--iterations 100]
+"""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "deep-attention-visual-odometry_amd")]
+
+import torch  # noqa: E402
+
+SHAPES = {"c1": (2, 64, False), "c2": (2, 128, False), "c3": (4, 256, True)}
+C3_SWEEP_US = 108.04  # profiles/r05_eval_summary.json, B = 8192
+
+
+def timed(fn, dev):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize(dev)
+    start.record()
+    out = fn()
+    end.record()
+    torch.cuda.synchronize(dev)
+    return start.elapsed_time(end), out
+
+
+def measure(shape, b, k, lr, repeats, dev):
+    from deep_attention_visual_odometry_amd import ReprojectionError, SGDSolver, make_scenes, native_ops
+
+    m, n, dist = SHAPES[shape]
+    s = make_scenes(b, m, n, distortion=dist, seed=7, drop=0.0 if dist else 0.1)
+    x0 = torch.tensor(s.initial, device=dev)
+    obs = torch.tensor(s.observations, device=dev)
+    vis = torch.tensor(s.visibility, device=dev).to(torch.uint8)
+    w = torch.randn(x0.shape, generator=torch.Generator().manual_seed(3)).to(dev)
+    solver = SGDSolver(lr, k)
+
+    def fused_forward():
+        return native_ops.ba_sgd_solve(x0, obs, vis, m, n, dist, learning_rate=lr, iterations=k)[0]
+
+    def composed_forward():
+        x = x0
+        for _ in range(k):
+            _, g, _ = torch.ops.dava.ba_evaluate(x, obs, vis, m, n, dist, None, None, True, False, 0)
+            x = x - lr * g
+        return x
+
+    def gradient(loop):
+        xg, og = x0.clone().requires_grad_(True), obs.clone().requires_grad_(True)
+        fn = ReprojectionError(og, vis, m, n, dist)
+        out = solver._loop(xg, fn) if loop else solver(xg, fn)
+        gx, go = torch.autograd.grad((out * w).sum(), [xg, og])
+        return out.detach(), gx, go
+
+    paths = {"fused_forward": fused_forward, "composed_forward": composed_forward,
+             "fused_gradient": lambda: gradient(False), "composed_gradient": lambda: gradient(True)}
+    best = {name: float("inf") for name in paths}
+    outs = {}
+    for pair in (("fused_forward", "composed_forward"), ("fused_gradient", "composed_gradient")):
+        for name in pair:  # warm-up: code objects, allocator
+            outs[name] = timed(paths[name], dev)[1]
+        for rep in range(repeats):
+            for name in (pair if rep % 2 == 0 else pair[::-1]):  # both orders
+                ms, _ = timed(paths[name], dev)
+                best[name] = min(best[name], ms)
+
+    # rows the descent keeps finite in both paths (at lr = 1e-4 a few of thousands of scenes diverge within K = 100,
+    # in the oracle too: no stopping rule, no line search)
+    finite = torch.isfinite(outs["fused_forward"]).all(dim=-1) & torch.isfinite(outs["composed_forward"]).all(dim=-1)
+
+    def rel(a, c):  # (a row that is about to diverge is ill-conditioned: the median says what a typical row does)
+        r = ((a - c).norm(dim=-1) / c.norm(dim=-1))[finite]
+        r = r[torch.isfinite(r)]
+        return {"max": float(r.max()), "median": float(r.median())}
+
+    rec = {"shape": shape, "B": b, "K": k, "learning_rate": lr, "P": x0.shape[1], "repeats": repeats,
+           "nonfinite_rows_fused": int((~torch.isfinite(outs["fused_forward"]).all(dim=-1)).sum()),
+           "nonfinite_rows_composed": int((~torch.isfinite(outs["composed_forward"]).all(dim=-1)).sum()),
+           "rows_compared": int(finite.sum())}
+    for name, ms in best.items():
+        rec[name + "_ms"] = round(ms, 3)
+        rec[name + "_problems_per_s"] = round(b / (ms * 1e-3), 1)
+    rec["forward_speedup"] = round(best["composed_forward"] / best["fused_forward"], 2)
+    rec["gradient_speedup"] = round(best["composed_gradient"] / best["fused_gradient"], 2)
+    # the two paths compute the same thing (reordered float32 sums apart)
+    rec["forward_max_rel_diff"] = rel(outs["fused_forward"], outs["composed_forward"])
+    rec["gradient_x0_max_rel_diff"] = rel(outs["fused_gradient"][1] - w, outs["composed_gradient"][1] - w)
+    rec["gradient_obs_max_rel_diff"] = rel(outs["fused_gradient"][2].flatten(1), outs["composed_gradient"][2].flatten(1))
+    if shape == "c3" and b == 8192:
+        rec["fused_forward_over_K_sweeps"] = round(best["fused_forward"] * 1e3 / (k * C3_SWEEP_US), 3)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "sgd_solve.jsonl"))
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--configs", default="c2:1024,c3:8192")
+    ap.add_argument("--iterations", type=int, default=100)
+    ap.add_argument("--learning-rate", type=float, default=1e-4)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("measure_sgd.py needs a ROCm device: nothing is measured without one")
+    dev = torch.device("cuda", 0)
+    lines = []
+    for config in args.configs.split(","):
+        shape, b = config.split(":")
+        rec = measure(shape, int(b), args.iterations, args.learning_rate, max(args.repeats, 5), dev)
+        print(json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
