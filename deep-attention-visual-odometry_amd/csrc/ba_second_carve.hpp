@@ -1,6 +1,6 @@
 // LDS image of the dual-number (forward-over-reverse) evaluation of one problem: shared by the second
 // derivatives (ba_second_order.hip) and the adjoint of the fused gradient descent (sgd_adjoint.hip), which
-// appends its float accumulator for dL/dobs after it.
+// appends its float accumulator for dL/dobs after it -- and, host only, what both derive from a scene: SecondPlan.
 #pragma once
 
 #include "ba_objective.hpp"
@@ -24,6 +24,19 @@ __host__ __device__ inline SecondCarve carve_second(int M, int N, int Pv) {
   c.vis_bytes_off = off * 4;
   c.total_bytes = c.vis_bytes_off + round_up(M * N, 16);
   return c;
+}
+
+// ---- host only: check_scene(s, ...) must have passed ----
+struct SecondPlan {
+  int status;  // DAVA_OK, or DAVA_ERR_UNSUPPORTED for an image that does not fit
+  int Pv, lds_bytes;
+};
+inline SecondPlan plan_second(const DavaScene* s) {
+  SecondPlan p{};
+  p.Pv = round_up(s->num_parameters, 4);
+  p.lds_bytes = carve_second(s->num_views, s->num_points, p.Pv).total_bytes;
+  p.status = p.lds_bytes > kMaxLds ? DAVA_ERR_UNSUPPORTED : DAVA_OK;
+  return p;
 }
 
 }  // namespace dava

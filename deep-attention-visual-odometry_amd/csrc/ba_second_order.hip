@@ -61,12 +61,6 @@ __global__ __launch_bounds__(kBlock) void ba_second_order_kernel(SecondArgs a) {
   }
 }
 
-template <int RES>
-static void launch_second(const SecondArgs& a, int B, int lds, hipStream_t s) {
-  set_dynamic_lds(ba_second_order_kernel<RES>, lds);
-  hipLaunchKernelGGL(ba_second_order_kernel<RES>, dim3(B), dim3(kBlock), lds, s, a);
-}
-
 }  // namespace dava
 
 using namespace dava;
@@ -85,12 +79,11 @@ extern "C" int dava_ba_second_order_obs(const DavaScene* scene, const float* x, 
   if (st != DAVA_OK) return st;
   if (scene->batch == 0) return DAVA_OK;
   if (!x) return DAVA_ERR_INVALID_ARGUMENT;
-  const int Pv = round_up(scene->num_parameters, 4);
-  const int lds = carve_second(scene->num_views, scene->num_points, Pv).total_bytes;
-  if (lds > 160 * 1024) return DAVA_ERR_UNSUPPORTED;
+  const SecondPlan p = plan_second(scene);
+  if (p.status != DAVA_OK) return p.status;
   SecondArgs a;
   a.L = make_layout(scene);
-  a.Pv = Pv;
+  a.Pv = p.Pv;
   a.obs = scene->observations;
   a.vis = scene->visibility;
   a.x = x;
@@ -101,8 +94,9 @@ extern "C" int dava_ba_second_order_obs(const DavaScene* scene, const float* x, 
   a.hv = hv_out;
   a.obs_grad = obs_grad_out;
   a.obs_hv = obs_hv_out;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (scene->residual == DAVA_RESIDUAL_RAY_ANGLE) launch_second<DAVA_RESIDUAL_RAY_ANGLE>(a, scene->batch, lds, s);
-  else launch_second<DAVA_RESIDUAL_SQUARED_REPROJECTION>(a, scene->batch, lds, s);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  with_flag(scene->residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+    launch_lds(ba_second_order_kernel<kRes>, scene->batch, kBlock, p.lds_bytes, static_cast<hipStream_t>(stream), a);
+  });
+  return launched();
 }

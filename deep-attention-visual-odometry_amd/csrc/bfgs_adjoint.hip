@@ -29,9 +29,7 @@
 //   k = 0:   gbar_0 = gbar_pend - dbar
 //   xbar += Hess E(x_k) gbar_k,  obsbar += (d2E / dobs dx) gbar_k    (forward-over-reverse, Dual)
 // H_k dbar and H_{k-1} wbar come from one pass over the history rows (s_j, w_j), like the forward's.
-#include "ba_objective.hpp"
-#include "dava_debug.hpp"
-#include "dava_tape.hpp"
+#include "adjoint_plan.hpp"
 
 namespace dava {
 
@@ -50,56 +48,16 @@ struct AdjointArgs {
   float* obs_grad;    // (B, M, N, 2) or null
   float* arows;       // (B, K, Pv) workspace
   int lcap;           // history entries (s_j, w_j), j < lcap, held in LDS for the H passes
-  float* gvws;        // global-vector mode: (B, kAdjGvFloats(Pv)) per-problem vector slices, else null
+  float* gvws;        // global-vector mode: (B, carve_adjoint gv_floats) per-problem vector slices, else null
   int gd_lds;         // global-vector mode: the HVP's dual gradient vector in LDS (carve_adjoint gdl)
   int sc_global;      // LDS mode: the tape's scalar row read in place (bfgs_ba_adjoint_kernel SCG)
 };
 
-constexpr int kAdjWaves = 4;
 // Entries per wave in flight in the passes: at two workgroups per CU, 1 and 3 are slower
 // (profiles/r03_ab_adjoint_inflight.log).  Measured and not kept: the row-streaming waves at
 // priority 0 (C3 -1.7%, C2 +1%, profiles/r03_ab_adjoint_prio.log) and C1/C2-shape rows through
 // buffer loads (C1 +1%, C2 +-1%, profiles/r03_ab_adjoint_buffer_loads.log).
 constexpr int kAdjInflight = 2;
-constexpr int kAdjBlock = kWave * kAdjWaves;
-constexpr int kAdjMaxGroups = 14;  // GV mode: float4 groups per thread (P <= 14 * 256 * 4 = 14336)
-constexpr int kAdjLdsBytes = 160 * 1024;
-
-struct AdjointCarve {
-  int xb, sbp, gbp, db, gk, p1, p2, wb, sv, wv, yv, gv, ak, an, sc, xd, gd, views, vpart, obs, obsacc, lh, scratch,
-      vis_bytes_off, total_bytes;
-  int gv_floats;  // global-vector mode: floats of one problem's workspace slice (the 14 vectors and 2 Dual ones)
-};
-
-// lcap: the oldest history entries' rows (s_j, w_j interleaved) kept on chip for the whole reverse
-// sweep -- every H pass reads them again, so each one held saves 2 Pv floats of HBM per step.
-// gv (global-vector mode, P too large for the LDS image, e.g. C5): the O(P) vectors are offsets into
-// the problem's workspace slice instead, the scene is read in place and the observation cotangent is
-// accumulated straight into the output; LDS keeps the scalars, view constants and reduction scratch.
-// gdl (global-vector mode): the dual gradient vector of the HVP evaluation in LDS instead of the slice
-// -- the evaluation accumulates it view after view, one dependent read-modify-write per pair.
-__host__ __device__ inline AdjointCarve carve_adjoint(int M, int N, int Pv, int T, int lcap = 0, bool gv = false,
-                                                     int nw = kAdjWaves, bool gdl = false) {
-  AdjointCarve c;
-  int off = 0, voff = 0;
-  int& o = gv ? voff : off;
-  int* vec[] = {&c.xb, &c.sbp, &c.gbp, &c.db, &c.gk, &c.p1, &c.p2, &c.wb, &c.sv, &c.wv, &c.yv, &c.gv, &c.ak, &c.an};
-  for (int* v : vec) { *v = o; o += Pv; }
-  c.sc = off; off += T;
-  c.xd = o; o += 2 * Pv;  // Dual
-  int& og = gv && gdl ? off : o;
-  c.gd = og; og += 2 * Pv;  // Dual
-  c.gv_floats = gv ? voff : 0;
-  c.views = off; off += 2 * round_up(views_floats(M), 4);
-  c.vpart = off; off += 2 * round_up(vpart_floats(M, nw), 4);
-  c.obs = off; off += gv ? 0 : round_up(2 * M * N, 4);
-  c.obsacc = off; off += gv ? 0 : round_up(2 * M * N, 4);
-  c.lh = off; off += gv ? 0 : 2 * lcap * Pv;
-  c.scratch = off; off += 2 * nw * 32;
-  c.vis_bytes_off = off * 4;
-  c.total_bytes = c.vis_bytes_off + (gv ? 0 : round_up(M * N, 16));
-  return c;
-}
 
 __device__ __forceinline__ f4a ldv(const float* p) { return *reinterpret_cast<const f4a*>(p); }
 __device__ __forceinline__ void stv(float* p, f4a v) { *reinterpret_cast<f4a*>(p) = v; }
@@ -406,13 +364,9 @@ __device__ __forceinline__ void wide_pair_pass(int P, int Pv, int j0, int j1, co
   __syncthreads();
 }
 
-// LDS mode: two workgroups per CU (registers <= 256 VGPRs, LDS <= 80 KB each), so one problem's
-// dual-number evaluation overlaps the other's row passes: C3 solve + gradient 51.7k -> 63.0k problems/s
-// (r03, profiles/r03_ab_adjoint_two_wg_per_cu.log; in r02 the same register cap spilled 100-165
-// registers and one workgroup per CU was faster, since then the passes' register use went down).
+// LDS mode runs two workgroups per CU (kAdjLdsWpe, adjoint_plan.hpp).
 // GT > 0: global-vector mode (the O(P) vectors in the workspace slice a.gvws, wide_pair_pass with up
 // to GT float4 groups per thread); GT = 0: everything O(P) in LDS (pair_pass, GM groups per lane).
-constexpr int kAdjLdsWpe = 2;
 // SCG (LDS mode): the tape's scalar row (alpha_k, rho_j, c_j, gamma: about 4 K floats) read in place
 // instead of staged in LDS.  The row is sized by the iteration cap, not by the steps taken: at C3 with
 // the reference's default cap (1000) it pushed the image past the 80 KB that two workgroups per CU
@@ -656,99 +610,27 @@ __global__ __launch_bounds__(kWave * NW, GT > 0 ? 1 : kAdjLdsWpe) void bfgs_ba_a
     for (int i = tid; i < 2 * MN; i += BLOCK) a.obs_grad[(size_t)b * 2 * MN + i] = obsacc[i];
 }
 
-// Global-vector mode: waves per workgroup (one workgroup per CU).  Eight: the row passes hold up to 7
-// float4 groups per thread and two waves per SIMD hide their latency; the dual-number evaluation then
-// runs at the 256-VGPR budget.  Four: up to 14 groups per thread, one wave per SIMD with 512 registers.
-// Eight unless the eight-wave LDS image (per-wave view partials and reduction scratch grow with the
-// waves) does not fit -- many views -- or the kDbgAdjGVWaves override asks for four.
-static int adjoint_gv_waves(const DavaScene* s, const TapeLayout& tl) {
-  if (debug_knob(kDbgAdjGVWaves) == 4) return 4;
-  return carve_adjoint(s->num_views, s->num_points, tl.Pv, tl.T, 0, true, 8).total_bytes <= kAdjLdsBytes ? 8 : 4;
-}
-
+// The kernel of a plan: LDS mode by the groups per lane (with SCG or without), global-vector mode by the waves and
+// the groups per thread rounded up to an instantiated width.
 template <int RES>
-static void launch_adjoint(const AdjointArgs& a, int B, int lds, int gm, int gt, int nw, hipStream_t s) {
-  if (gt == 0 && a.sc_global) {  // LDS mode, the tape's scalar row in place
-    auto go = [&](auto kernel) {
-      set_dynamic_lds(kernel, lds);
-      hipLaunchKernelGGL(kernel, dim3(B), dim3(kAdjBlock), lds, s, a);
-    };
-    if (gm <= 1) go(bfgs_ba_adjoint_kernel<RES, 1, 0, kAdjWaves, true>);
-    else if (gm == 2) go(bfgs_ba_adjoint_kernel<RES, 2, 0, kAdjWaves, true>);
-    else if (gm == 3) go(bfgs_ba_adjoint_kernel<RES, 3, 0, kAdjWaves, true>);
+static void launch_adjoint(const AdjointArgs& a, int B, const AdjointPlan& p, hipStream_t s) {
+  auto go = [&](auto kernel) { launch_lds(kernel, B, kWave * p.nw, p.lds_bytes, s, a); };
+  if (p.sc_global) {  // LDS mode, the tape's scalar row in place
+    if (p.gm <= 1) go(bfgs_ba_adjoint_kernel<RES, 1, 0, kAdjWaves, true>);
+    else if (p.gm == 2) go(bfgs_ba_adjoint_kernel<RES, 2, 0, kAdjWaves, true>);
+    else if (p.gm == 3) go(bfgs_ba_adjoint_kernel<RES, 3, 0, kAdjWaves, true>);
     else go(bfgs_ba_adjoint_kernel<RES, 4, 0, kAdjWaves, true>);
-    return;
-  }
-  auto go = [&](auto kernel, int threads) {
-    set_dynamic_lds(kernel, lds);
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), lds, s, a);
-  };
-  if (gt > 0 && nw == 8) {  // global-vector mode, eight waves: 4 or 7 float4 groups per thread
-    if (gt <= 4) go(bfgs_ba_adjoint_kernel<RES, 1, 4, 8>, 8 * kWave);
-    else go(bfgs_ba_adjoint_kernel<RES, 1, 7, 8>, 8 * kWave);
-  } else if (gt > 0) {  // global-vector mode, four waves: 4, 8 or 14 float4 groups per thread
-    if (gt <= 4) go(bfgs_ba_adjoint_kernel<RES, 1, 4>, kAdjBlock);
-    else if (gt <= 8) go(bfgs_ba_adjoint_kernel<RES, 1, 8>, kAdjBlock);
-    else go(bfgs_ba_adjoint_kernel<RES, 1, kAdjMaxGroups>, kAdjBlock);
-  } else if (gm <= 1) go(bfgs_ba_adjoint_kernel<RES, 1>, kAdjBlock);
-  else if (gm == 2) go(bfgs_ba_adjoint_kernel<RES, 2>, kAdjBlock);
-  else if (gm == 3) go(bfgs_ba_adjoint_kernel<RES, 3>, kAdjBlock);
-  else go(bfgs_ba_adjoint_kernel<RES, 4>, kAdjBlock);
-}
-
-// Global-vector mode when the LDS image does not fit one CU (or P > 1024, past pair_pass's 4 groups
-// per lane); the kDbgAdjForceGV override forces it (tests: the same tape through both kernels).
-static bool adjoint_gv(const DavaScene* s, const TapeLayout& tl) {
-  if (debug_flag(kDbgAdjForceGV)) return true;
-  return s->num_parameters > 1024 || carve_adjoint(s->num_views, s->num_points, tl.Pv, tl.T).total_bytes > kAdjLdsBytes;
-}
-static int adjoint_groups(const TapeLayout& tl) { return (tl.Pv / 4 + kAdjBlock - 1) / kAdjBlock; }
-
-static int adjoint_check(const DavaScene* s, const DavaSolverConfig* c) {
-  if (!c) return DAVA_ERR_INVALID_ARGUMENT;
-  const int st = check_scene(s, false);  // (the launch checks the data pointers itself)
-  if (st != DAVA_OK) return st;
-  const int P = s->num_parameters;
-  if (c->hessian_mode != DAVA_HESSIAN_COMPACT || c->iterations < 1 || c->iterations > 1025) return DAVA_ERR_UNSUPPORTED;
-  const TapeLayout tl = tape_layout(s->batch, P, c->iterations);
-  if (adjoint_gv(s, tl)) {
-    if (adjoint_groups(tl) > kAdjMaxGroups) return DAVA_ERR_UNSUPPORTED;
-    // the image of the launch that will run: adjoint_gv_waves() falls back to four waves where eight do not fit
-    if (carve_adjoint(s->num_views, s->num_points, tl.Pv, tl.T, 0, true, adjoint_gv_waves(s, tl)).total_bytes >
-        kAdjLdsBytes)
-      return DAVA_ERR_UNSUPPORTED;
-  }
-  return DAVA_OK;
-}
-
-// LDS mode: the tape's scalar row stays in place (SCG) when staging it would push the image past the two
-// workgroups per CU that the rest of it allows
-static bool adjoint_sc_global(const DavaScene* s, const TapeLayout& tl) {
-  if (adjoint_gv(s, tl)) return false;
-  if (debug_knob(kDbgAdjScGlobal) >= 0) return debug_knob(kDbgAdjScGlobal) > 0;  // tests
-  const int M = s->num_views, N = s->num_points;
-  return carve_adjoint(M, N, tl.Pv, tl.T).total_bytes > kAdjLdsBytes / kAdjLdsWpe &&
-         carve_adjoint(M, N, tl.Pv, 0).total_bytes <= kAdjLdsBytes / kAdjLdsWpe;
-}
-
-// As many history entries on chip as the CU's LDS leaves room for (one workgroup per CU), at most
-// the K - 1 a solve can make; the kDbgAdjLdsEntries override caps it (0: none) for A/B runs.  None in GV mode.
-static int adjoint_lds_entries(const DavaScene* s, const TapeLayout& tl) {
-  if (adjoint_gv(s, tl)) return 0;
-  const int base = carve_adjoint(s->num_views, s->num_points, tl.Pv, adjoint_sc_global(s, tl) ? 0 : tl.T).total_bytes;
-  int n = (kAdjLdsBytes / kAdjLdsWpe - base) / (int)(2 * tl.Pv * sizeof(float));
-  n = max(0, min(n, tl.K - 1));
-  if (debug_knob(kDbgAdjLdsEntries) >= 0) n = max(0, min(n, (int)debug_knob(kDbgAdjLdsEntries)));
-  return n;
-}
-
-// workspace: the a rows (B, K, Pv), then in GV mode the per-problem vector slices
-static size_t adjoint_rows_bytes(const DavaScene* s, const TapeLayout& tl) {
-  return (size_t)s->batch * tl.K * tl.Pv * sizeof(float);
-}
-static size_t adjoint_gv_bytes(const DavaScene* s, const TapeLayout& tl) {
-  if (!adjoint_gv(s, tl)) return 0;
-  return (size_t)s->batch * carve_adjoint(s->num_views, s->num_points, tl.Pv, tl.T, 0, true).gv_floats * sizeof(float);
+  } else if (p.gv && p.nw == 8) {  // global-vector mode, eight waves: 4 or 7 float4 groups per thread
+    if (p.gt <= 4) go(bfgs_ba_adjoint_kernel<RES, 1, 4, 8>);
+    else go(bfgs_ba_adjoint_kernel<RES, 1, 7, 8>);
+  } else if (p.gv) {  // global-vector mode, four waves: 4, 8 or 14 float4 groups per thread
+    if (p.gt <= 4) go(bfgs_ba_adjoint_kernel<RES, 1, 4>);
+    else if (p.gt <= 8) go(bfgs_ba_adjoint_kernel<RES, 1, 8>);
+    else go(bfgs_ba_adjoint_kernel<RES, 1, kAdjMaxGroups>);
+  } else if (p.gm <= 1) go(bfgs_ba_adjoint_kernel<RES, 1>);
+  else if (p.gm == 2) go(bfgs_ba_adjoint_kernel<RES, 2>);
+  else if (p.gm == 3) go(bfgs_ba_adjoint_kernel<RES, 3>);
+  else go(bfgs_ba_adjoint_kernel<RES, 4>);
 }
 
 }  // namespace dava
@@ -756,35 +638,31 @@ static size_t adjoint_gv_bytes(const DavaScene* s, const TapeLayout& tl) {
 using namespace dava;
 
 extern "C" size_t dava_ba_solve_backward_workspace_bytes(const DavaScene* scene, const DavaSolverConfig* config) {
-  if (adjoint_check(scene, config) != DAVA_OK) return 0;
-  const TapeLayout tl = tape_layout(scene->batch, scene->num_parameters, config->iterations);
-  return adjoint_rows_bytes(scene, tl) + adjoint_gv_bytes(scene, tl) + 256;
+  const AdjointPlan p = plan_adjoint(scene, config);
+  return p.status == DAVA_OK ? p.rows_bytes + p.gv_bytes + 256 : 0;
 }
 
 extern "C" int dava_ba_solve_backward_lds_entries(const DavaScene* scene, const DavaSolverConfig* config) {
-  if (adjoint_check(scene, config) != DAVA_OK) return 0;
-  return adjoint_lds_entries(scene, tape_layout(scene->batch, scene->num_parameters, config->iterations));
+  const AdjointPlan p = plan_adjoint(scene, config);
+  return p.status == DAVA_OK ? p.lcap : 0;
 }
 
 extern "C" int dava_ba_solve_backward(const DavaScene* scene, const DavaSolverConfig* config, const void* tape,
                                       size_t tape_bytes, const int32_t* status, const float* x_out_grad,
                                       float* x0_grad, float* observations_grad, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  const int st = adjoint_check(scene, config);
-  if (st != DAVA_OK) return st;
+  const AdjointPlan p = plan_adjoint(scene, config);
+  if (p.status != DAVA_OK) return p.status;
   if (scene->batch == 0) return DAVA_OK;
   if (!scene->observations || !scene->visibility || !tape || !status || !x_out_grad || !x0_grad)
     return DAVA_ERR_INVALID_ARGUMENT;
-  const TapeLayout tl = tape_layout(scene->batch, scene->num_parameters, config->iterations);
-  if (tape_bytes < tl.queue_byte) return DAVA_ERR_WORKSPACE;
-  const size_t rows = adjoint_rows_bytes(scene, tl), gvb = adjoint_gv_bytes(scene, tl);
-  if (!workspace || workspace_bytes < rows + gvb) return DAVA_ERR_WORKSPACE;
-  const bool gv = adjoint_gv(scene, tl);
+  if (tape_bytes < p.tl.queue_byte) return DAVA_ERR_WORKSPACE;
+  if (!workspace || workspace_bytes < p.rows_bytes + p.gv_bytes) return DAVA_ERR_WORKSPACE;
   AdjointArgs a;
   a.L = make_layout(scene);
-  a.Pv = tl.Pv;
-  a.K = tl.K;
-  a.tl = tl;
+  a.Pv = p.tl.Pv;
+  a.K = p.tl.K;
+  a.tl = p.tl;
   a.tape = static_cast<const float*>(tape);
   a.obs = scene->observations;
   a.vis = scene->visibility;
@@ -793,19 +671,14 @@ extern "C" int dava_ba_solve_backward(const DavaScene* scene, const DavaSolverCo
   a.x0_grad = x0_grad;
   a.obs_grad = observations_grad;
   a.arows = static_cast<float*>(workspace);
-  a.gvws = gv ? reinterpret_cast<float*>(static_cast<char*>(workspace) + rows) : nullptr;
-  a.lcap = adjoint_lds_entries(scene, tl);
-  a.sc_global = adjoint_sc_global(scene, tl) ? 1 : 0;
-  const int nw = gv ? adjoint_gv_waves(scene, tl) : kAdjWaves;
-  a.gd_lds = gv && !debug_flag(kDbgAdjGdHbm) &&
-             carve_adjoint(scene->num_views, scene->num_points, tl.Pv, tl.T, a.lcap, gv, nw, true).total_bytes <=
-                 kAdjLdsBytes;
-  const int lds = carve_adjoint(scene->num_views, scene->num_points, tl.Pv, a.sc_global ? 0 : tl.T, a.lcap, gv, nw,
-                                a.gd_lds).total_bytes;
-  const int gm = (tl.Pv / 4 + kWave - 1) / kWave;
-  const int gt = gv ? (tl.Pv / 4 + kWave * nw - 1) / (kWave * nw) : 0;  // float4 groups per thread
+  a.gvws = p.gv ? reinterpret_cast<float*>(static_cast<char*>(workspace) + p.rows_bytes) : nullptr;
+  a.lcap = p.lcap;
+  a.gd_lds = p.gd_lds ? 1 : 0;
+  a.sc_global = p.sc_global ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (scene->residual == DAVA_RESIDUAL_RAY_ANGLE) launch_adjoint<DAVA_RESIDUAL_RAY_ANGLE>(a, scene->batch, lds, gm, gt, nw, s);
-  else launch_adjoint<DAVA_RESIDUAL_SQUARED_REPROJECTION>(a, scene->batch, lds, gm, gt, nw, s);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  with_flag(scene->residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+    launch_adjoint<kRes>(a, scene->batch, p, s);
+  });
+  return launched();
 }

@@ -161,8 +161,6 @@ __global__ __launch_bounds__(kBlock) void search_direction_backward_kernel(int64
   }
 }
 
-inline int launched_ok() { return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH; }
-
 constexpr int kUpdateBackwardVectors = 9;
 
 template <typename T>
@@ -176,7 +174,7 @@ int update_backward(int64_t batch, int64_t n, const T* h, const T* s, const T* y
   set_dynamic_lds(update_backward_kernel<T>, (int)lds);
   hipLaunchKernelGGL(update_backward_kernel<T>, dim3((unsigned)batch), dim3(kBlock), lds,
                      static_cast<hipStream_t>(stream), n, h, s, y, g, gh, gs, gy);
-  return launched_ok();
+  return launched();
 }
 
 template <typename T>
@@ -187,7 +185,7 @@ int initial_scale_backward(int64_t batch, int64_t n, const T* s, const T* y, con
   if (!s || !y || !gout) return DAVA_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(initial_scale_backward_kernel<T>, dim3((unsigned)batch), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), n, s, y, gout, gs, gy);
-  return launched_ok();
+  return launched();
 }
 
 template <typename T>
@@ -198,7 +196,7 @@ int scale_matrix_backward(int64_t batch, int64_t n, const T* scale, const T* h, 
   if (!scale || !h || !g) return DAVA_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(scale_matrix_backward_kernel<T>, dim3((unsigned)batch), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), n * n, scale, h, g, gscale, gh);
-  return launched_ok();
+  return launched();
 }
 
 template <typename T>
@@ -209,7 +207,7 @@ int search_direction_backward(int64_t batch, int64_t n, const T* h, const T* g, 
   if (!h || !g || !dbar) return DAVA_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(search_direction_backward_kernel<T>, dim3((unsigned)batch), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), n, h, g, dbar, gh, gg);
-  return launched_ok();
+  return launched();
 }
 
 }  // namespace dava

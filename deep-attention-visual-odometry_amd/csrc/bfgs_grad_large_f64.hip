@@ -125,5 +125,5 @@ extern "C" int dava_bfgs_update_inverse_hessian_backward_large_f64(int64_t batch
   hipLaunchKernelGGL(update_backward_large_f64_kernel, dim3((unsigned)batch), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), n, h, s, y, grad_out, grad_h, grad_s, grad_y,
                      static_cast<double*>(workspace));
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  return launched();
 }

@@ -249,7 +249,7 @@ int compact_direction(int64_t n_active, int64_t P, int64_t Pv, int64_t cap, int6
   set_dynamic_lds(kernel, (int)lds);
   hipLaunchKernelGGL(kernel, dim3((unsigned)n_active), dim3(kBlock), lds, static_cast<hipStream_t>(stream), P, Pv,
                      cap, count, idx, g, y, s, S, W, rho, c, gamma, d);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  return launched();
 }
 
 // state columns
@@ -323,8 +323,6 @@ __global__ void wolfe_update_kernel(int64_t batch, int trial, T c1, T c2, int st
   flags[b * 2] = widen;
   flags[b * 2 + 1] = zoom;
 }
-
-inline int launched() { return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH; }
 
 template <typename T>
 int update_inverse_hessian(int64_t batch, int64_t n, const T* h, const T* s, const T* y, T* out, void* stream) {

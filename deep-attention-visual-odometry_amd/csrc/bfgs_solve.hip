@@ -846,8 +846,10 @@ static void launch_solve_res(const SolveArgs& a, int B, int lds, hipStream_t s, 
 
 template <int MODE, bool GV, bool XL = false, bool SLICE = false>
 static void launch_solve(const SolveArgs& a, int B, int lds, hipStream_t s, int residual, int nw) {
-  if (residual == DAVA_RESIDUAL_RAY_ANGLE) launch_solve_res<MODE, GV, DAVA_RESIDUAL_RAY_ANGLE, XL, SLICE>(a, B, lds, s, nw);
-  else launch_solve_res<MODE, GV, DAVA_RESIDUAL_SQUARED_REPROJECTION, XL, SLICE>(a, B, lds, s, nw);
+  with_flag(residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+    launch_solve_res<MODE, GV, kRes, XL, SLICE>(a, B, lds, s, nw);
+  });
 }
 
 // The kernel of a plan: MODE from plan.mode, then SLICE (history modes only), XL, GV or LDS mode.
@@ -947,7 +949,7 @@ static int solve_impl(const DavaScene* scene, const DavaSolverConfig* config, co
   if (p.mode == DAVA_HESSIAN_DENSE) launch_solve_mode<DAVA_HESSIAN_DENSE>(a, p, scene->residual, s);
   else if (p.mode == kHybrid) launch_solve_mode<kHybrid>(a, p, scene->residual, s);
   else launch_solve_mode<DAVA_HESSIAN_COMPACT>(a, p, scene->residual, s);
-  const bool launched = hipGetLastError() == hipSuccess;
+  const int result = launched();
 #if DAVA_PHASE_TIMING
   {
     unsigned long long* h = static_cast<unsigned long long*>(malloc(ph_bytes));
@@ -985,7 +987,7 @@ static int solve_impl(const DavaScene* scene, const DavaSolverConfig* config, co
     free(h);
   }
 #endif
-  return launched ? DAVA_OK : DAVA_ERR_LAUNCH;
+  return result;
 }
 
 extern "C" int dava_ba_solve(const DavaScene* scene, const DavaSolverConfig* config, const float* x0,
@@ -1001,28 +1003,26 @@ extern "C" int dava_ba_solve_record(const DavaScene* scene, const DavaSolverConf
   return solve_impl(scene, config, x0, x_out, error_out, status_out, tape, tape_bytes, true, stream);
 }
 
-template <bool G, bool S, bool T, bool GV, int RES, bool XL, int NW, int PPT>
-static void launch_eval_form(const EvalArgs& a, int B, int lds, hipStream_t s) {
-  const auto kernel = ba_evaluate_kernel<G, S, T, GV, RES, XL, NW, PPT>;
-  set_dynamic_lds(kernel, lds);
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(kWave * NW), lds, s, a);
-}
-
-// form: 0 = LDS mode, PPT 0 | 1 = LDS mode, a point per thread in registers | 2 = GV + XL (8 waves) |
-// 3 = GV in place (8 waves)
-template <bool G, bool S, bool T, int RES>
-static void launch_eval_res(const EvalArgs& a, int B, int lds, hipStream_t s, int form) {
-  constexpr int GVW = solve_waves(true);
-  if (form == 3) launch_eval_form<G, S, T, true, RES, false, GVW, 0>(a, B, lds, s);
-  else if (form == 2) launch_eval_form<G, S, T, true, RES, true, GVW, 0>(a, B, lds, s);
-  else if (form == 1) launch_eval_form<G, S, T, false, RES, false, kWaves, 1>(a, B, lds, s);
-  else launch_eval_form<G, S, T, false, RES, false, kWaves, 0>(a, B, lds, s);
-}
-
-template <bool G, bool S, bool T>
-static void launch_eval(const EvalArgs& a, int B, int lds, hipStream_t s, int form, int res) {
-  if (res == DAVA_RESIDUAL_RAY_ANGLE) launch_eval_res<G, S, T, DAVA_RESIDUAL_RAY_ANGLE>(a, B, lds, s, form);
-  else launch_eval_res<G, S, T, DAVA_RESIDUAL_SQUARED_REPROJECTION>(a, B, lds, s, form);
+// The instantiation for a plan's form -- GV in place or GV + XL (8 waves), LDS mode with or without a point per
+// thread in registers -- the outputs asked for (gradient, slope, trial point x + alpha d) and the residual
+static int launch_eval(const EvalArgs& a, int B, const EvalPlan& p, int residual, hipStream_t s) {
+  auto go = [&](auto kernel) { launch_lds(kernel, B, kWave * p.nw, p.lds_bytes, s, a); };
+  with_flag(a.grad != nullptr, [&](auto grad) {
+    with_flag(a.slope != nullptr, [&](auto slope) {
+      with_flag(a.dir != nullptr && a.alpha != nullptr, [&](auto trial) {
+        with_flag(residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+          constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+          constexpr bool G = decltype(grad)::value, S = decltype(slope)::value, T = decltype(trial)::value;
+          constexpr int GVW = solve_waves(true);
+          if (p.gv && !p.xl) go(ba_evaluate_kernel<G, S, T, true, kRes, false, GVW, 0>);
+          else if (p.gv) go(ba_evaluate_kernel<G, S, T, true, kRes, true, GVW, 0>);
+          else if (p.ppt) go(ba_evaluate_kernel<G, S, T, false, kRes, false, kWaves, 1>);
+          else go(ba_evaluate_kernel<G, S, T, false, kRes, false, kWaves, 0>);
+        });
+      });
+    });
+  });
+  return launched();
 }
 
 extern "C" int dava_ba_evaluate(const DavaScene* scene, const float* x, const float* direction, const float* alpha,
@@ -1032,18 +1032,11 @@ extern "C" int dava_ba_evaluate(const DavaScene* scene, const float* x, const fl
   if (scene->batch == 0) return DAVA_OK;
   if (!x || !error_out) return DAVA_ERR_INVALID_ARGUMENT;
   if (slope_out && !direction) return DAVA_ERR_INVALID_ARGUMENT;
-  // the solve's own choices (plan_solve) for an image without history: GV mode by the four-wave LDS-mode
-  // image, XL by the eight-wave one
-  const int M = scene->num_views, N = scene->num_points, Pv = round_up(scene->num_parameters, 4);
-  const int gvw = solve_waves(true);
-  const bool gv = debug_flag(kDbgForceGV) || carve_lds(M, N, Pv).total_bytes > kLdsModeBudget;
-  const bool xl = gv && !debug_flag(kDbgGVNoXL) && carve_lds(M, N, Pv, 0, true, 0, true, gvw).total_bytes <= kMaxLds;
-  const int form = gv ? (xl ? 2 : 3) : (N <= kBlock && !debug_flag(kDbgNoPPT) ? 1 : 0);
-  const int lds = carve_lds(M, N, Pv, 0, gv, 0, xl, gv ? gvw : kWaves).total_bytes;
-  if (lds > kMaxLds) return DAVA_ERR_UNSUPPORTED;
+  const EvalPlan p = plan_eval(scene);
+  if (p.status != DAVA_OK) return p.status;
   EvalArgs a;
   a.L = make_layout(scene);
-  a.Pv = Pv;
+  a.Pv = p.Pv;
   a.obs = scene->observations;
   a.vis = scene->visibility;
   a.x = x;
@@ -1052,16 +1045,5 @@ extern "C" int dava_ba_evaluate(const DavaScene* scene, const float* x, const fl
   a.err = error_out;
   a.grad = grad_out;
   a.slope = slope_out;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool G = grad_out != nullptr, S = slope_out != nullptr, T = direction != nullptr && alpha != nullptr;
-  const int B = scene->batch;
-  if (G && S && T) launch_eval<true, true, true>(a, B, lds, s, form, scene->residual);
-  else if (G && S) launch_eval<true, true, false>(a, B, lds, s, form, scene->residual);
-  else if (G && T) launch_eval<true, false, true>(a, B, lds, s, form, scene->residual);
-  else if (G) launch_eval<true, false, false>(a, B, lds, s, form, scene->residual);
-  else if (S && T) launch_eval<false, true, true>(a, B, lds, s, form, scene->residual);
-  else if (S) launch_eval<false, true, false>(a, B, lds, s, form, scene->residual);
-  else if (T) launch_eval<false, false, true>(a, B, lds, s, form, scene->residual);
-  else launch_eval<false, false, false>(a, B, lds, s, form, scene->residual);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  return launch_eval(a, scene->batch, p, scene->residual, static_cast<hipStream_t>(stream));
 }

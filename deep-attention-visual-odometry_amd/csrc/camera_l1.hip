@@ -357,7 +357,7 @@ int l1_camera_vjp(int64_t batch, int32_t estimates, int32_t views, int32_t point
                               pixel_ratio, max_grad, scale);
   hipLaunchKernelGGL(l1_camera_vjp_kernel<T>, dim3((unsigned)(batch * estimates * D)), dim3(kBlock), lds,
                      static_cast<hipStream_t>(stream), a, (int)D, error_cot, grad_cot, (int)detach_points, vjp);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  return launched();
 }
 
 template <typename T>
@@ -377,7 +377,7 @@ int l1_camera_evaluate(int64_t batch, int32_t estimates, int32_t views, int32_t 
   a.err = err; a.grad = grad;
   hipLaunchKernelGGL(l1_camera_kernel<T>, dim3((unsigned)(batch * estimates)), dim3(kBlock), lds,
                      static_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  return launched();
 }
 
 }  // namespace dava

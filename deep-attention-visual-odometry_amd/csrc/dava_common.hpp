@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dava_ba.h"
 
 namespace dava {
@@ -43,12 +45,30 @@ inline Layout make_layout(const DavaScene* s) {
   return Layout{s->num_views, s->num_points, s->num_parameters, s->distortion ? 1 : 0};
 }
 
+constexpr int kMaxLds = 160 * 1024;  // one CU's LDS: the limit of every one-workgroup-per-problem image
+
 // A launch with more than 64 KiB of dynamic LDS has to raise the kernel's limit first.
 template <typename Kernel>
 inline void set_dynamic_lds(Kernel kernel, int bytes) {
   if (bytes > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
+// ... and then the launch: `grid` workgroups of `threads`, `lds` bytes of dynamic LDS
+template <typename Kernel, typename Args>
+inline void launch_lds(Kernel kernel, int grid, int threads, int lds, hipStream_t s, const Args& a) {
+  set_dynamic_lds(kernel, lds);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, a);
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument of a launch
+template <class F>
+void with_flag(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// what an entry point returns after its launch
+inline int launched() { return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH; }
 
 // Training mode's drop path (bfgs_solver.py:121-125): problem b keeps updating at iteration k iff
 // u(seed, b, k) > p, u uniform on [0, 1) with 24-bit resolution from a counter-based 64-bit mix

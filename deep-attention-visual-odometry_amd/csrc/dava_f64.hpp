@@ -1,10 +1,8 @@
 // What the float64 sources share (solve_f64.hpp, adjoint_f64.hpp, ba_second_order_f64.hip): the limits of the
-// one-workgroup-per-problem LDS images, the host-side scene check and the two helpers of their launchers.
+// one-workgroup-per-problem LDS images, and the host-side scene check.
 #pragma once
 
 #include "dava_common.hpp"
-
-#include <type_traits>
 
 namespace dava {
 namespace f64 {
@@ -29,15 +27,6 @@ inline int history_capacity(int iterations) { return iterations - 1 > 1 ? iterat
 // tells the entry points apart: false for the symbols of the LDS image (form 0 by fit alone, the F64_FORM override
 // ignored, everything else DAVA_ERR_UNSUPPORTED); true for the *_large_* symbols and the form queries, which take
 // the form choose_form / choose_adjoint_form / choose_second_form name.
-
-// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument of a launch
-template <class F>
-void with_flag(bool v, F&& f) {
-  if (v) f(std::true_type{});
-  else f(std::false_type{});
-}
-
-inline int launched() { return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH; }
 
 }  // namespace f64
 }  // namespace dava

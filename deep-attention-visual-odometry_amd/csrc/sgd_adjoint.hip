@@ -72,19 +72,12 @@ __global__ __launch_bounds__(kBlock) void sgd_ba_adjoint_kernel(SgdAdjointArgs a
     for (int i = tid; i < 2 * MN; i += kBlock) a.gobs[(size_t)b * 2 * MN + i] = acc[i];
 }
 
-template <int RES>
-static void launch_sgd_adjoint(const SgdAdjointArgs& a, int B, int lds, hipStream_t s) {
-  set_dynamic_lds(sgd_ba_adjoint_kernel<RES>, lds);
-  hipLaunchKernelGGL(sgd_ba_adjoint_kernel<RES>, dim3(B), dim3(kBlock), lds, s, a);
-}
-
 // DAVA_OK where the adjoint runs this scene / config: the config's validity and the fit of the adjoint's own
 // image, whatever form (or override) the forward takes.  check_scene(scene, ...) must have passed.
 static int sgd_adjoint_status(const DavaScene* scene, const DavaSgdConfig* config, int* lds_out) {
   if (!config || config->iterations < 0) return DAVA_ERR_INVALID_ARGUMENT;
   if (!sgd_sizes_sane(scene)) return DAVA_ERR_UNSUPPORTED;
-  const int M = scene->num_views, N = scene->num_points;
-  const int lds = sgd_adjoint_lds_bytes(carve_second(M, N, round_up(scene->num_parameters, 4)), M, N);
+  const int lds = plan_second(scene).lds_bytes + sgd_adjoint_acc_bytes(scene->num_views, scene->num_points);
   if (lds > kMaxLds) return DAVA_ERR_UNSUPPORTED;
   if (lds_out) *lds_out = lds;
   return DAVA_OK;
@@ -122,8 +115,9 @@ extern "C" int dava_ba_sgd_backward(const DavaScene* scene, const DavaSgdConfig*
   a.gout = x_out_grad;
   a.gx0 = x0_grad;
   a.gobs = observations_grad;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (scene->residual == DAVA_RESIDUAL_RAY_ANGLE) launch_sgd_adjoint<DAVA_RESIDUAL_RAY_ANGLE>(a, scene->batch, lds, s);
-  else launch_sgd_adjoint<DAVA_RESIDUAL_SQUARED_REPROJECTION>(a, scene->batch, lds, s);
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  with_flag(scene->residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+    launch_lds(sgd_ba_adjoint_kernel<kRes>, scene->batch, kBlock, lds, static_cast<hipStream_t>(stream), a);
+  });
+  return launched();
 }

@@ -34,9 +34,7 @@ inline size_t sgd_tape_bytes(int B, int K, int Pv) { return (size_t)B * (size_t)
 // Adjoint image: carve_second's (dual x and gradient, dual view constants and partials, dual dE/dobs, scratch,
 // observations, visibility) followed by the float accumulator of dL/dobs (2 M N floats).
 __host__ __device__ inline int sgd_adjoint_acc_bytes_off(const SecondCarve& c) { return c.total_bytes; }
-__host__ __device__ inline int sgd_adjoint_lds_bytes(const SecondCarve& c, int M, int N) {
-  return c.total_bytes + round_up(2 * M * N, 4) * 4;
-}
+inline int sgd_adjoint_acc_bytes(int M, int N) { return round_up(2 * M * N, 4) * 4; }
 
 // ---- host only ----
 struct SgdPlan {
@@ -60,12 +58,11 @@ inline SgdPlan plan_sgd(const DavaScene* scene, const DavaSgdConfig* config) {
   }
   p.status = DAVA_ERR_UNSUPPORTED;
   if (!sgd_sizes_sane(scene)) return p;
-  const int M = scene->num_views, N = scene->num_points;
-  p.Pv = round_up(scene->num_parameters, 4);
-  // dava_ba_evaluate's rule: the large form where the fused solve's own LDS-mode image is past its budget
-  p.gv = debug_flag(kDbgForceGV) || carve_lds(M, N, p.Pv).total_bytes > kLdsModeBudget;
-  p.ppt = !p.gv && N <= kBlock && !debug_flag(kDbgNoPPT);
-  p.lds_bytes = carve_sgd(M, N, p.Pv, p.gv, p.gv ? solve_waves(true) : kWaves).total_bytes;
+  const EvalPlan e = plan_eval(scene);  // the evaluation's form; the image is the descent's own
+  p.gv = e.gv;
+  p.ppt = e.ppt;
+  p.Pv = e.Pv;
+  p.lds_bytes = carve_sgd(scene->num_views, scene->num_points, p.Pv, p.gv, e.nw).total_bytes;
   if (p.lds_bytes > kMaxLds) return p;
   p.status = DAVA_OK;
   return p;

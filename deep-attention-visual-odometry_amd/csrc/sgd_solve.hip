@@ -3,7 +3,7 @@
 // as ONE launch, one workgroup per problem for the whole descent.  No stopping rule, no mask: every problem
 // does the same work, so the grid is B workgroups and there is no work queue.
 //
-// Two forms, chosen as dava_ba_evaluate chooses its own (the layouts measured there):
+// Two forms, the ones dava_ba_evaluate takes (plan_eval, solve_plan.hpp; the layouts measured there):
 //   LDS form (C1-C3)  observations, visibility, x and the gradient staged in LDS once; four waves; a point
 //                     per thread in registers across the views when N <= 256 (PPT = 1);
 //   large form (C5)   x and the gradient in LDS (2 Pv floats), the scene read in place with the packed pair
@@ -78,18 +78,12 @@ __global__ __launch_bounds__(kWave * NW) void sgd_ba_solve_kernel(SgdArgs a) {
   for (int i = tid; i < P; i += BLOCK) a.x_out[(size_t)b * P + i] = x[i];
 }
 
-template <bool GV, int RES, int PPT, int NW, bool RECORD>
-static void launch_sgd_form(const SgdArgs& a, int B, int lds, hipStream_t s) {
-  const auto kernel = sgd_ba_solve_kernel<GV, RES, PPT, NW, RECORD>;
-  set_dynamic_lds(kernel, lds);
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(kWave * NW), lds, s, a);
-}
-
 template <int RES, bool RECORD>
 static void launch_sgd(const SgdArgs& a, int B, const SgdPlan& p, hipStream_t s) {
-  if (p.gv) launch_sgd_form<true, RES, 0, solve_waves(true), RECORD>(a, B, p.lds_bytes, s);
-  else if (p.ppt) launch_sgd_form<false, RES, 1, kWaves, RECORD>(a, B, p.lds_bytes, s);
-  else launch_sgd_form<false, RES, 0, kWaves, RECORD>(a, B, p.lds_bytes, s);
+  auto go = [&](auto kernel, int nw) { launch_lds(kernel, B, kWave * nw, p.lds_bytes, s, a); };
+  if (p.gv) go(sgd_ba_solve_kernel<true, RES, 0, solve_waves(true), RECORD>, solve_waves(true));
+  else if (p.ppt) go(sgd_ba_solve_kernel<false, RES, 1, kWaves, RECORD>, kWaves);
+  else go(sgd_ba_solve_kernel<false, RES, 0, kWaves, RECORD>, kWaves);
 }
 
 static int sgd_solve_impl(const DavaScene* scene, const DavaSgdConfig* config, const float* x0, float* x_out,
@@ -120,15 +114,13 @@ static int sgd_solve_impl(const DavaScene* scene, const DavaSgdConfig* config, c
   a.x_out = x_out;
   a.trace = error_trace_out;
   a.tape = record ? static_cast<float*>(tape) : nullptr;
-  const bool ray = scene->residual == DAVA_RESIDUAL_RAY_ANGLE;
-  if (record) {
-    if (ray) launch_sgd<DAVA_RESIDUAL_RAY_ANGLE, true>(a, scene->batch, p, s);
-    else launch_sgd<DAVA_RESIDUAL_SQUARED_REPROJECTION, true>(a, scene->batch, p, s);
-  } else {
-    if (ray) launch_sgd<DAVA_RESIDUAL_RAY_ANGLE, false>(a, scene->batch, p, s);
-    else launch_sgd<DAVA_RESIDUAL_SQUARED_REPROJECTION, false>(a, scene->batch, p, s);
-  }
-  return hipGetLastError() == hipSuccess ? DAVA_OK : DAVA_ERR_LAUNCH;
+  with_flag(record, [&](auto rec) {
+    with_flag(scene->residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+      constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+      launch_sgd<kRes, decltype(rec)::value>(a, scene->batch, p, s);
+    });
+  });
+  return launched();
 }
 
 }  // namespace dava

@@ -1,6 +1,6 @@
 // The geometry of a fused-solve launch (bfgs_solve.hip): how one problem's state is carved out of LDS and
 // of its workspace slice, and -- host only, below -- the one derivation of everything a launch and the
-// size queries need from (scene, config): SolvePlan.
+// size queries need from (scene, config): SolvePlan, and EvalPlan for the objective evaluation.
 //
 // The __host__ __device__ part is what the kernels themselves call (carve_lds): the host sizes the image
 // with the same code the device indexes it with.
@@ -101,7 +101,6 @@ __host__ __device__ inline LdsCarve carve_lds(int M, int N, int Pv, int kcap = 0
 }
 
 // ---- host only: the launch plan ----
-constexpr int kMaxLds = 160 * 1024;
 // Global-vector mode when the all-in-LDS image would cost more than two workgroups
 // per CU (e.g. C5: P = 12381 -> 446 KB of vectors per problem).
 constexpr int kLdsModeBudget = 72 * 1024;
@@ -250,6 +249,28 @@ inline SolvePlan plan_solve(const DavaScene* s, const DavaSolverConfig* c, bool 
     p.state_bytes = p.vec_bytes + p.hist_bytes + p.dense_bytes;
   }
   p.dense_offset = p.hist_offset + p.hist_bytes;  // HYBRID: the dense matrices follow the histories
+  p.status = p.lds_bytes > kMaxLds ? DAVA_ERR_UNSUPPORTED : DAVA_OK;
+  return p;
+}
+
+// ---- host only: the objective evaluation's form (dava_ba_evaluate; the gradient descent takes gv and ppt) ----
+// The solve's own choices (plan_solve) for an image without history: GV mode by the four-wave LDS-mode image, XL
+// by the eight-wave one; LDS mode holds a point per thread in registers (ppt) while N <= kBlock.  The kDbgForceGV,
+// kDbgGVNoXL and kDbgNoPPT overrides apply as in the solve.  check_scene(s, ...) must have passed.
+struct EvalPlan {
+  int status;  // DAVA_OK, or DAVA_ERR_UNSUPPORTED for an image that does not fit
+  bool gv, xl, ppt;
+  int nw, lds_bytes, Pv;
+};
+inline EvalPlan plan_eval(const DavaScene* s) {
+  EvalPlan p{};
+  const int M = s->num_views, N = s->num_points;
+  p.Pv = round_up(s->num_parameters, 4);
+  p.gv = debug_flag(kDbgForceGV) || carve_lds(M, N, p.Pv).total_bytes > kLdsModeBudget;
+  p.nw = p.gv ? solve_waves(true) : kWaves;
+  p.xl = p.gv && !debug_flag(kDbgGVNoXL) && carve_lds(M, N, p.Pv, 0, true, 0, true, p.nw).total_bytes <= kMaxLds;
+  p.ppt = !p.gv && N <= kBlock && !debug_flag(kDbgNoPPT);
+  p.lds_bytes = carve_lds(M, N, p.Pv, 0, p.gv, 0, p.xl, p.nw).total_bytes;
   p.status = p.lds_bytes > kMaxLds ? DAVA_ERR_UNSUPPORTED : DAVA_OK;
   return p;
 }

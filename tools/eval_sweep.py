@@ -10,7 +10,7 @@ Algorithmic bytes per problem: observations 8 MN + visibility MN + x, d and grad
 12 B.  Arithmetic: counted by rocprofv3 (SQ_INSTS_VALU_FLOPS_FP32, tools/profile_eval.sh) -- the pass is
 VALU work per (view, point) pair, so the VALU peak is its roofline, not HBM.
 
-usage (GPU box): python tools/eval_sweep.py [--config C3|C5|both] [--reps R]  -> one JSON line per config
+usage (GPU box): python tools/eval_sweep.py [--config C2|C3|C5|both] [--reps R]  -> one JSON line per config
 """
 import argparse
 import json
@@ -23,7 +23,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "deep-attention-visual-odometry_amd")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-CONFIGS = {"C3": (8192, 4, 256, True), "C5": (256, 16, 4096, False)}
+CONFIGS = {"C2": (1024, 2, 128, False), "C3": (8192, 4, 256, True), "C5": (256, 16, 4096, False)}
 HBM_PEAK_GBS = 8000.0
 VALU_FP32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md chip table (vector FP32, packed FMA)
 
@@ -42,7 +42,7 @@ def scenes(b, m, n, distortion):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="both", choices=["C3", "C5", "both"])
+    ap.add_argument("--config", default="both", choices=["C2", "C3", "C5", "both"])
     ap.add_argument("--reps", type=int, default=50)
     args = ap.parse_args()
     from deep_attention_visual_odometry_amd import native_ops
