@@ -8,7 +8,7 @@
 // the body of ba_second_order.hip): x carries x_k as its value -- read from the recording's tape -- and
 // lambda as its tangent; the gradient's tangents are H lambda and dE/dobs's tangents the mixed term.
 // lambda stays in x's tangent slots from step to step.  Deterministic: no atomics, every element has one
-// owner thread.
+// owner thread.  Beyond the LDS image (dava_ba_sgd_backward_large) the kernel takes forms 1 and 2 below.
 #include <hip/hip_runtime.h>
 
 #include "sgd_plan.hpp"
@@ -27,32 +27,60 @@ struct SgdAdjointArgs {
   float* gobs;         // (B, M, N, 2) dL/dobs, or nullptr (then not formed)
 };
 
-template <int RES>
-__global__ __launch_bounds__(kBlock) void sgd_ba_adjoint_kernel(SgdAdjointArgs a) {
+// What the form 1 and 2 instantiations take (the form-0 one keeps its kernel argument as it was)
+struct LargeSgdAdjointArgs : SgdAdjointArgs {
+  float* obsd;  // B x 4MN (Dual dE/dobs of one step), or null: gobs is null, not formed
+  float* vecs;  // form 2: B x 4 Pv (Dual x, g), uninitialised
+};
+
+template <int FORM>
+using sgd_adjoint_args_t = std::conditional_t<FORM != 0, LargeSgdAdjointArgs, SgdAdjointArgs>;
+
+// FORM as in ba_second_order.hip: 0 everything in LDS; 1 the dual x and gradient in LDS, the scene read in place,
+// the step's dual dE/dobs in the workspace and the accumulator of dL/dobs the output itself (zeroed and updated
+// by the thread that owns the element, the arithmetic and order of form 0); 2 the dual x and gradient in the
+// problem's workspace slice as well.
+template <int RES, int FORM = 0>
+__global__ __launch_bounds__(kBlock) void sgd_ba_adjoint_kernel(sgd_adjoint_args_t<FORM> a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Layout L = a.L;
   const int P = L.P, M = L.M, N = L.N, MN = M * N, Pv = a.Pv, K = a.K;
   const int b = blockIdx.x, tid = threadIdx.x;
-  const SecondCarve cv = carve_second(M, N, Pv);
-  Dual* x = reinterpret_cast<Dual*>(lds + cv.x);
-  Dual* g = reinterpret_cast<Dual*>(lds + cv.g);
+  const SecondCarve cv = FORM == 0 ? carve_second(M, N, Pv) : carve_second_large(M, Pv, FORM);
+  float* vec = lds;  // the dual x and gradient: LDS, or (form 2) this problem's workspace slice
+  if constexpr (FORM == 2) vec = a.vecs + (size_t)b * 4 * Pv;
+  Dual* x = reinterpret_cast<Dual*>(vec + cv.x);
+  Dual* g = reinterpret_cast<Dual*>(vec + cv.g);
   Dual* views = reinterpret_cast<Dual*>(lds + cv.views);
   Dual* vpart = reinterpret_cast<Dual*>(lds + cv.vpart);
   Dual* obsd = reinterpret_cast<Dual*>(lds + cv.obsd);
   float* scratch = lds + cv.scratch;
-  float* obs = lds + cv.obs;
-  uint8_t* vis = reinterpret_cast<uint8_t*>(lds) + cv.vis_bytes_off;
   float* acc = lds + sgd_adjoint_acc_bytes_off(cv) / 4;
+  const float* obs;
+  const uint8_t* vis;
   const bool want_obs = a.gobs != nullptr;  // uniform
   for (int i = tid; i < Pv; i += kBlock) {
     x[i] = Dual(0.0f, i < P ? a.gout[(size_t)b * P + i] : 0.0f);
     g[i] = Dual(0.0f);
   }
-  for (int i = tid; i < 2 * MN; i += kBlock) {
-    obs[i] = a.obs[(size_t)b * 2 * MN + i];
-    acc[i] = 0.0f;
+  if constexpr (FORM == 0) {
+    float* obl = lds + cv.obs;
+    uint8_t* vil = reinterpret_cast<uint8_t*>(lds) + cv.vis_bytes_off;
+    for (int i = tid; i < 2 * MN; i += kBlock) {
+      obl[i] = a.obs[(size_t)b * 2 * MN + i];
+      acc[i] = 0.0f;
+    }
+    for (int i = tid; i < MN; i += kBlock) vil[i] = a.vis[(size_t)b * MN + i] ? 1 : 0;
+    obs = obl;
+    vis = vil;
+  } else {  // the scene where the caller put it; the accumulator is the output
+    obs = a.obs + (size_t)b * 2 * MN;
+    vis = a.vis + (size_t)b * MN;
+    obsd = want_obs ? reinterpret_cast<Dual*>(a.obsd + (size_t)b * 4 * MN) : nullptr;
+    acc = want_obs ? a.gobs + (size_t)b * 2 * MN : nullptr;
+    if (want_obs)
+      for (int i = tid; i < 2 * MN; i += kBlock) acc[i] = 0.0f;
   }
-  for (int i = tid; i < MN; i += kBlock) vis[i] = a.vis[(size_t)b * MN + i] ? 1 : 0;
   const float lr = a.lr;
   int buf = 0;
   for (int k = K - 1; k >= 0; --k) {
@@ -68,8 +96,10 @@ __global__ __launch_bounds__(kBlock) void sgd_ba_adjoint_kernel(SgdAdjointArgs a
       for (int i = tid; i < 2 * MN; i += kBlock) acc[i] = acc[i] - lr * obsd[i].t;
   }
   for (int i = tid; i < P; i += kBlock) a.gx0[(size_t)b * P + i] = x[i].t;
-  if (want_obs)
-    for (int i = tid; i < 2 * MN; i += kBlock) a.gobs[(size_t)b * 2 * MN + i] = acc[i];
+  if constexpr (FORM == 0) {
+    if (want_obs)
+      for (int i = tid; i < 2 * MN; i += kBlock) a.gobs[(size_t)b * 2 * MN + i] = acc[i];
+  }
 }
 
 // DAVA_OK where the adjoint runs this scene / config: the config's validity and the fit of the adjoint's own
@@ -81,6 +111,41 @@ static int sgd_adjoint_status(const DavaScene* scene, const DavaSgdConfig* confi
   if (lds > kMaxLds) return DAVA_ERR_UNSUPPORTED;
   if (lds_out) *lds_out = lds;
   return DAVA_OK;
+}
+
+// The adjoint for a scene of any size (dava_ba_sgd_backward_large and its queries): the form, its LDS image and
+// its workspace [dual dE/dobs of one step B x 4MN floats, only with an observation gradient | form 2: B x 4 Pv
+// floats | 256-byte tail].  check_scene(scene, ...) must have passed.
+struct SgdAdjointLarge {
+  int status, form, lds;
+  size_t obsd_bytes, vector_bytes;
+  size_t workspace_bytes() const { return obsd_bytes + vector_bytes + kSecondTailBytes; }
+};
+static SgdAdjointLarge sgd_adjoint_large(const DavaScene* scene, const DavaSgdConfig* config, bool obs_grad) {
+  SgdAdjointLarge p{};
+  p.form = -1;
+  p.status = DAVA_ERR_INVALID_ARGUMENT;
+  if (!config || config->iterations < 0) return p;
+  p.status = DAVA_ERR_UNSUPPORTED;
+  const int M = scene->num_views, N = scene->num_points, Pv = round_up(scene->num_parameters, 4);
+  p.form = choose_second_form(scene, sgd_adjoint_acc_bytes(M, N));
+  if (p.form < 0) return p;
+  p.status = DAVA_OK;
+  p.lds = p.form == 0 ? plan_second(scene).lds_bytes + sgd_adjoint_acc_bytes(M, N)
+                      : carve_second_large(M, Pv, p.form).total_bytes;
+  p.obsd_bytes = p.form != 0 && obs_grad ? (size_t)scene->batch * 4 * M * N * sizeof(float) : 0;
+  p.vector_bytes = p.form == 2 ? (size_t)scene->batch * 4 * Pv * sizeof(float) : 0;
+  return p;
+}
+
+template <int FORM>
+static int launch_sgd_adjoint(const LargeSgdAdjointArgs& args, const DavaScene* scene, int lds, void* stream) {
+  const sgd_adjoint_args_t<FORM>& a = args;
+  with_flag(scene->residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+    launch_lds(sgd_ba_adjoint_kernel<kRes, FORM>, scene->batch, kBlock, lds, static_cast<hipStream_t>(stream), a);
+  });
+  return launched();
 }
 
 }  // namespace dava
@@ -120,4 +185,52 @@ extern "C" int dava_ba_sgd_backward(const DavaScene* scene, const DavaSgdConfig*
     launch_lds(sgd_ba_adjoint_kernel<kRes>, scene->batch, kBlock, lds, static_cast<hipStream_t>(stream), a);
   });
   return launched();
+}
+
+// host-only: 0, 1, 2, or minus the status
+extern "C" int dava_ba_sgd_backward_form(const DavaScene* scene, const DavaSgdConfig* config) {
+  const int st = check_scene(scene, false);
+  if (st != DAVA_OK) return -st;
+  const SgdAdjointLarge p = sgd_adjoint_large(scene, config, false);
+  return p.status == DAVA_OK ? p.form : -p.status;
+}
+
+// host-only; obs_grad: observations_grad will be asked for.  0: unsupported.
+extern "C" size_t dava_ba_sgd_backward_large_workspace_bytes(const DavaScene* scene, const DavaSgdConfig* config,
+                                                             int obs_grad) {
+  if (check_scene(scene, false) != DAVA_OK) return 0;
+  const SgdAdjointLarge p = sgd_adjoint_large(scene, config, obs_grad != 0);
+  return p.status == DAVA_OK ? p.workspace_bytes() : 0;
+}
+
+extern "C" int dava_ba_sgd_backward_large(const DavaScene* scene, const DavaSgdConfig* config, const void* tape,
+                                          size_t tape_bytes, const float* x_out_grad, float* x0_grad,
+                                          float* observations_grad, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  const int st = check_scene(scene, true);
+  if (st != DAVA_OK) return st;
+  if (!config || config->iterations < 0) return DAVA_ERR_INVALID_ARGUMENT;
+  if (scene->batch == 0) return DAVA_OK;
+  if (!x_out_grad || !x0_grad) return DAVA_ERR_INVALID_ARGUMENT;
+  const SgdAdjointLarge p = sgd_adjoint_large(scene, config, observations_grad != nullptr);
+  if (p.status != DAVA_OK) return p.status;
+  const int K = config->iterations, Pv = round_up(scene->num_parameters, 4);
+  if (K > 0 && (!tape || tape_bytes < sgd_tape_bytes(scene->batch, K, Pv))) return DAVA_ERR_WORKSPACE;
+  if (p.obsd_bytes + p.vector_bytes > 0 && (!workspace || workspace_bytes < p.workspace_bytes()))
+    return DAVA_ERR_WORKSPACE;
+  LargeSgdAdjointArgs a;
+  a.L = make_layout(scene);
+  a.Pv = Pv;
+  a.K = K;
+  a.lr = config->learning_rate;
+  a.obs = scene->observations;
+  a.vis = scene->visibility;
+  a.tape = static_cast<const float*>(tape);
+  a.gout = x_out_grad;
+  a.gx0 = x0_grad;
+  a.gobs = observations_grad;
+  a.obsd = p.obsd_bytes ? static_cast<float*>(workspace) : nullptr;
+  a.vecs = p.form == 2 ? reinterpret_cast<float*>(static_cast<char*>(workspace) + p.obsd_bytes) : nullptr;
+  if (p.form == 0) return launch_sgd_adjoint<0>(a, scene, p.lds, stream);
+  return p.form == 1 ? launch_sgd_adjoint<1>(a, scene, p.lds, stream) : launch_sgd_adjoint<2>(a, scene, p.lds, stream);
 }

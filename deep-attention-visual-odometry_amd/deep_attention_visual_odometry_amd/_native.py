@@ -27,7 +27,7 @@ LIB_PATH = (_DEBUG_ENV and os.environ.get("DAVA_LIB")) or os.path.join(_HERE, "_
 # Overridable launch choices of the library (csrc/dava_debug.hpp), and of this package's Python side
 LIBRARY_KNOBS = ("FORCE_GV", "GV_NO_XL", "SOLVE_WAVES", "WG_PER_CU", "LDS_HISTORY", "STAGGER", "STAGGER_LEVELS",
                  "NO_PPT", "NO_QUEUE", "ADJ_GV_WAVES", "ADJ_FORCE_GV", "ADJ_LDS_ENTRIES", "ADJ_GD_HBM",
-                 "COMPACT_SWITCH", "GV_SCALAR_SLICE", "ADJ_SC_GLOBAL", "F64_FORM")
+                 "COMPACT_SWITCH", "GV_SCALAR_SLICE", "ADJ_SC_GLOBAL", "F64_FORM", "F32_DUAL_FORM")
 # GENERIC_BACKWARD: differentiate a fused objective's solve with the generic loop, not the adjoint;
 # GENERIC_TRAINING: training mode's drop path with the generic loop and torch's own RNG;
 # GENERIC_DENSE: the generic loop keeps the reference's dense (B, P, P) inverse Hessian even without a graph
@@ -205,6 +205,15 @@ SIGNATURES = {
     "dava_ba_sgd_backward_supported": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig)]),
     "dava_ba_sgd_backward": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig), _vp,
                                             ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    # float32 second derivatives and the descent's adjoint beyond the LDS image (forms 1 and 2)
+    "dava_ba_second_order_form": (ctypes.c_int, [ctypes.POINTER(DavaScene)]),
+    "dava_ba_second_order_large_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DavaScene), ctypes.c_int]),
+    "dava_ba_second_order_large": (ctypes.c_int, [ctypes.POINTER(DavaScene)] + [_vp] * 9 + [ctypes.c_size_t, _vp]),
+    "dava_ba_sgd_backward_form": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig)]),
+    "dava_ba_sgd_backward_large_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DavaScene),
+                                                                     ctypes.POINTER(DavaSgdConfig), ctypes.c_int]),
+    "dava_ba_sgd_backward_large": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig), _vp,
+                                                  ctypes.c_size_t, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dava_debug_set_override": (ctypes.c_int, [ctypes.c_char_p, _c_i64]),
     "dava_debug_clear_overrides": (None, []),
     "dava_abi_version": (ctypes.c_int, []),

@@ -474,6 +474,16 @@ def _(x0, observations, visibility, num_views, num_points, distortion, learning_
             x0.new_empty((b, iterations, sgd_tape_rows(x0.shape[1]))))
 
 
+def _check_sgd_tape(tape: Tensor, x_out_grad: Tensor, iterations: int) -> None:
+    """The kernel dereferences the tape as device memory of this launch: refuse anything else loudly."""
+    b, dev = x_out_grad.shape[0], x_out_grad.device
+    if (tape.device != dev or tape.dtype != torch.float32 or not tape.is_contiguous()
+            or tuple(tape.shape) != (b, iterations, sgd_tape_rows(x_out_grad.shape[1]))):
+        raise ValueError(f"tape must be the recording call's contiguous float32 ({b}, {iterations}, "
+                         f"{sgd_tape_rows(x_out_grad.shape[1])}) tensor on {dev}, got {tuple(tape.shape)} "
+                         f"{tape.dtype} on {tape.device}")
+
+
 @torch.library.custom_op("dava::ba_sgd_backward", mutates_args=(), device_types=_CUDA)
 def ba_sgd_backward(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
                     num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int,
@@ -482,13 +492,8 @@ def ba_sgd_backward(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visi
     lib = N.load_library()
     sc, cfg = _sgd_scene(x_out_grad, observations, visibility, num_views, num_points, distortion, learning_rate,
                          iterations, residual, "the gradient descent's adjoint")
-    b, dev = x_out_grad.shape[0], x_out_grad.device
-    # the kernel dereferences the tape as device memory of this launch: refuse anything else loudly
-    if (tape.device != dev or tape.dtype != torch.float32 or not tape.is_contiguous()
-            or tuple(tape.shape) != (b, iterations, sgd_tape_rows(x_out_grad.shape[1]))):
-        raise ValueError(f"tape must be the recording call's contiguous float32 ({b}, {iterations}, "
-                         f"{sgd_tape_rows(x_out_grad.shape[1])}) tensor on {dev}, got {tuple(tape.shape)} "
-                         f"{tape.dtype} on {tape.device}")
+    dev = x_out_grad.device
+    _check_sgd_tape(tape, x_out_grad, iterations)
     gx = torch.empty_like(x_out_grad)
     gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
     with torch.cuda.device(dev):
@@ -522,6 +527,145 @@ def _sgd_backward(ctx, x_grad, _errors_grad, _tape_grad):
 
 
 ba_sgd_solve_differentiable.register_autograd(_sgd_backward, setup_context=_sgd_setup_context)
+
+
+# ---------------------------------------- float32 dual-number kernels beyond the LDS image
+# ba_second_order, ba_sgd_solve_differentiable and ba_sgd_backward keep one problem's dual image in LDS and keep
+# their refusals; the `*_large` operators take any admitted scene size (forms 1 and 2 of csrc/ba_second_carve.hpp,
+# form 0's launch where it fits and no F32_DUAL_FORM override is set), with a workspace from torch's allocator sized
+# by the library's host queries.
+
+def f32_old_symbol_runs(probe) -> bool:
+    """:func:`f64_old_symbol_runs` for the float32 dual-number kernels and their F32_DUAL_FORM override."""
+    return N.library_knob("F32_DUAL_FORM") <= 0 and bool(probe())
+
+
+def _same_f32(t: Optional[Tensor], like: Tensor, what: str) -> None:
+    if t is not None and (t.shape != like.shape or t.dtype != torch.float32 or t.device != like.device
+                          or not t.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(like.shape)} on {like.device}")
+
+
+@torch.library.custom_op("dava::ba_second_order_large", mutates_args=(), device_types=_CUDA)
+def ba_second_order_large(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
+                          distortion: bool, direction: Optional[Tensor], residual: int, want_hv: bool,
+                          want_obs: bool,
+                          obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``dava_ba_second_order_large``: ``ba_second_order`` for a scene of any size."""
+    lib = N.load_library()
+    _require_float32(x, "second derivatives of the fused objectives")
+    _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
+    _same_f32(direction, x, "direction")
+    _same_f32(obs_direction, observations, "obs_direction")
+    b = x.shape[0]
+    err = torch.empty(b, device=x.device, dtype=torch.float32)
+    grad = torch.empty_like(x)
+    hv = torch.empty_like(x) if want_hv else _empty0(x)
+    obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
+    obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
+    sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
+    need = int(lib.dava_ba_second_order_large_workspace_bytes(sc, 1 if want_obs else 0))
+    if need == 0:
+        raise ValueError("this scene has no float32 second derivatives (more views than the dual view constants "
+                         "can hold in LDS)")
+    ws = _scratch(need, x.device)
+    with torch.cuda.device(x.device):
+        N.check(lib.dava_ba_second_order_large(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err),
+                                               N.ptr(grad), N.ptr(hv) if want_hv else None,
+                                               N.ptr(obs_grad) if want_obs else None,
+                                               N.ptr(obs_hv) if (want_obs and want_hv) else None, N.ptr(ws),
+                                               ws.numel(), N.stream_of(x.device)), "dava_ba_second_order_large")
+    return err, grad, hv, obs_grad, obs_hv
+
+
+@ba_second_order_large.register_fake
+def _(x, observations, visibility, num_views, num_points, distortion, direction, residual, want_hv, want_obs,
+      obs_direction=None):
+    b = x.shape[0]
+    return (x.new_empty((b,)), torch.empty_like(x), torch.empty_like(x) if want_hv else x.new_empty((0,)),
+            torch.empty_like(observations) if want_obs else x.new_empty((0,)),
+            torch.empty_like(observations) if (want_obs and want_hv) else x.new_empty((0,)))
+
+
+@torch.library.custom_op("dava::ba_sgd_solve_differentiable_large", mutates_args=(), device_types=_CUDA)
+def ba_sgd_solve_differentiable_large(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
+                                      num_points: int, distortion: bool, learning_rate: float, iterations: int,
+                                      residual: int, want_errors: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """``ba_sgd_solve_differentiable`` for a scene of any size the recording descent runs: the same recording
+    launch and tape; its backward is ``ba_sgd_backward_large`` (not differentiable twice)."""
+    lib = N.load_library()
+    sc, cfg = _sgd_scene(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+                         residual, "the recording gradient descent")
+    if lib.dava_ba_sgd_backward_form(sc, cfg) < 0:
+        raise ValueError("this scene has no fused adjoint of the gradient descent: more views than the dual view "
+                         "constants can hold in LDS")
+    b, dev = x0.shape[0], x0.device
+    tape = torch.empty((b, iterations, sgd_tape_rows(x0.shape[1])), device=dev, dtype=torch.float32)
+    if _POISON:
+        tape.fill_(float("nan"))
+    x_out = torch.empty_like(x0)
+    errs = torch.empty((b, iterations), device=dev, dtype=torch.float32) if want_errors else _empty0(x0)
+    with torch.cuda.device(dev):
+        status = lib.dava_ba_sgd_solve_record(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
+                                              N.ptr(tape) if tape.numel() else None, tape.numel() * 4,
+                                              N.stream_of(dev))
+    if status == N.DAVA_ERR_UNSUPPORTED:
+        raise ValueError(_SGD_REFUSAL)
+    N.check(status, "dava_ba_sgd_solve_record")
+    return x_out, errs, tape
+
+
+@ba_sgd_solve_differentiable_large.register_fake
+def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
+      want_errors):
+    b = x0.shape[0]
+    return (torch.empty_like(x0), x0.new_empty((b, iterations) if want_errors else (0,)),
+            x0.new_empty((b, iterations, sgd_tape_rows(x0.shape[1]))))
+
+
+@torch.library.custom_op("dava::ba_sgd_backward_large", mutates_args=(), device_types=_CUDA)
+def ba_sgd_backward_large(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
+                          num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int,
+                          want_observations: bool) -> Tuple[Tensor, Tensor]:
+    """``dava_ba_sgd_backward_large``: ``ba_sgd_backward`` for a scene of any size."""
+    lib = N.load_library()
+    sc, cfg = _sgd_scene(x_out_grad, observations, visibility, num_views, num_points, distortion, learning_rate,
+                         iterations, residual, "the gradient descent's adjoint")
+    dev = x_out_grad.device
+    _check_sgd_tape(tape, x_out_grad, iterations)
+    need = int(lib.dava_ba_sgd_backward_large_workspace_bytes(sc, cfg, 1 if want_observations else 0))
+    if need == 0:
+        raise ValueError("this scene has no fused adjoint of the gradient descent: more views than the dual view "
+                         "constants can hold in LDS")
+    ws = _scratch(need, dev)
+    gx = torch.empty_like(x_out_grad)
+    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
+    with torch.cuda.device(dev):
+        N.check(lib.dava_ba_sgd_backward_large(sc, cfg, N.ptr(tape) if tape.numel() else None, tape.numel() * 4,
+                                               N.ptr(x_out_grad), N.ptr(gx),
+                                               N.ptr(gobs) if want_observations else None, N.ptr(ws), ws.numel(),
+                                               N.stream_of(dev)), "dava_ba_sgd_backward_large")
+    return gx, gobs
+
+
+@ba_sgd_backward_large.register_fake
+def _(x_out_grad, tape, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+      residual, want_observations):
+    return (torch.empty_like(x_out_grad),
+            torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
+
+
+@torch.autograd.function.once_differentiable
+def _sgd_backward_large(ctx, x_grad, _errors_grad, _tape_grad):
+    tape, observations, visibility = ctx.saved_tensors
+    need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    x_grad = x_grad.to(torch.float32)
+    gx, gobs = ba_sgd_backward_large(x_grad if x_grad.is_contiguous() else x_grad.contiguous(), tape,
+                                     observations.detach(), visibility, *ctx.meta, bool(need_obs))
+    return (gx if need_x else None, gobs if need_obs else None) + (None,) * 8
+
+
+ba_sgd_solve_differentiable_large.register_autograd(_sgd_backward_large, setup_context=_sgd_setup_context)
 
 
 # ---------------------------------------- float64 second derivatives, recording solve and adjoint
@@ -1237,4 +1381,5 @@ OPS = ("bfgs_solve", "ba_solve", "ba_solve_record", "ba_solve_backward", "ba_eva
        "bfgs_update_inverse_hessian_backward", "bfgs_initial_scale", "bfgs_initial_scale_backward",
        "bfgs_scale_matrix", "bfgs_scale_matrix_backward", "bfgs_search_direction", "bfgs_search_direction_backward",
        "wolfe_init", "wolfe_propose", "wolfe_update", "l1_camera_evaluate", "l1_camera_vjp",
-       "ba_sgd_solve", "ba_sgd_solve_differentiable", "ba_sgd_backward")
+       "ba_sgd_solve", "ba_sgd_solve_differentiable", "ba_sgd_backward", "ba_second_order_large",
+       "ba_sgd_solve_differentiable_large", "ba_sgd_backward_large")

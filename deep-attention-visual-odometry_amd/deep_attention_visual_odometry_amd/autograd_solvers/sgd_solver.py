@@ -12,7 +12,9 @@ output requires grad iff the input does.  Three execution paths:
 2. **Fused, differentiable** -- the same with ``parameters.requires_grad``: the recording launch
    (``dava_ba_sgd_solve_record``) and, as its backward, the adjoint kernel (``dava_ba_sgd_backward``), which
    carries gradients to the parameters and to the objective's observations; taken where
-   ``dava_ba_sgd_backward_supported``.
+   ``dava_ba_sgd_backward_supported``.  An objective built with ``large_derivatives=True`` takes it at every scene
+   the recording descent and some form of the adjoint run (``dava_ba_sgd_backward_large``: forms 1 and 2 beyond the
+   LDS image, C5 among them).
 3. **The reference's loop** in torch, with ``error_function(parameters)`` and ``torch.autograd.grad(...,
    create_graph=...)`` -- any closure, CPU tensors, float64, and a fused objective whose image the fused kernels
    do not take (there the objective is an ordinary closure on its own kernels).
@@ -47,6 +49,11 @@ class SGDSolver(Module):
             if not parameters.requires_grad:
                 if torch.compiler.is_compiling() or native_ops.sgd_solve_supported(*shape, error_function.residual):
                     return self._fused(parameters, error_function, native_ops.ba_sgd_solve)
+            elif error_function.large_derivatives:
+                if torch.compiler.is_compiling() or (
+                        native_ops.sgd_backward_form(*shape, self.iterations, error_function.residual) >= 0
+                        and native_ops.sgd_solve_supported(*shape, error_function.residual)):
+                    return self._fused(parameters, error_function, native_ops.ba_sgd_solve_differentiable_large)
             elif torch.compiler.is_compiling() or native_ops.sgd_backward_supported(*shape, self.iterations,
                                                                                     error_function.residual):
                 return self._fused(parameters, error_function, native_ops.ba_sgd_solve_differentiable)

@@ -52,13 +52,15 @@ _F64_FIRST_ORDER_ONLY = ("the float64 fused objectives give E and dE/dx only: se
 
 
 _F64_LARGE = 2  # f64_derivatives of an objective built with float64_large_gradients=True (True / 1: without)
+_F32_LARGE = 3  # the same slot for float32 parameters of an objective built with large_derivatives=True
 
 
 def _second_order(x, f64_derivatives=False):
     """The forward-over-reverse launch of x's dtype (float64 only on objectives built with float64_derivatives;
-    with float64_large_gradients too: the launch that takes any scene size where the LDS image does not fit)."""
+    with float64_large_gradients too: the launch that takes any scene size where the LDS image does not fit;
+    float32 on an objective built with large_derivatives likewise)."""
     if x.dtype != torch.float64:
-        return native_ops.ba_second_order
+        return native_ops.ba_second_order_large if f64_derivatives == _F32_LARGE else native_ops.ba_second_order
     if f64_derivatives == _F64_LARGE:
         return native_ops.ba_second_order_large_f64
     return native_ops.ba_second_order_f64
@@ -144,14 +146,18 @@ class ReprojectionError:
     second derivatives: create_graph, observations that require grad, double backward of dE/dobs, and the
     drop-in solver differentiates through a float64 solve; ``float64_large_gradients=True`` -- which requires
     ``float64_derivatives=True``, else ``ValueError`` -- extends both to scenes beyond the kernels' LDS image:
-    the second derivatives, the recording solve and the adjoint in their forms 1 and 2).  With ``distortion=True`` the
+    the second derivatives, the recording solve and the adjoint in their forms 1 and 2).
+    ``large_derivatives=True`` (independent of the float64 keywords) does the same for float32 parameters: the
+    float32 second derivatives -- create_graph, observations that require grad, the double backward of dE/dobs --
+    run at any admitted scene size (``dava_ba_second_order_large``), and ``SGDSolver`` differentiates through its
+    fused descent there; without it such scenes keep raising ``RuntimeError``.  With ``distortion=True`` the
     five Brown-Conrady coefficients (k1 k2 k3 p1 p2) are appended to the
     parameter vector (``camera_model/distorted_camera_model.py:59-86``).
     """
 
     def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int,
                  distortion: bool = False, float64_derivatives: bool = False,
-                 float64_large_gradients: bool = False):
+                 float64_large_gradients: bool = False, large_derivatives: bool = False):
         if observations.shape[-3:] != (num_views, num_points, 2):
             raise ValueError(f"observations must end in ({num_views}, {num_points}, 2), got {tuple(observations.shape)}")
         if visibility.shape != observations.shape[:-1]:
@@ -174,6 +180,8 @@ class ReprojectionError:
         self.float64_large_gradients = bool(float64_large_gradients)
         if self.float64_large_gradients and not self.float64_derivatives:
             raise ValueError("float64_large_gradients=True needs float64_derivatives=True")
+        # opt-in: float32 second derivatives (and SGDSolver's adjoint) for scenes beyond the LDS image
+        self.large_derivatives = bool(large_derivatives)
         self.visibility = visibility.to(torch.uint8)
         self.num_views = int(num_views)
         self.num_points = int(num_points)
@@ -214,9 +222,12 @@ class ReprojectionError:
             return self._torch_objective(x, obs.to(x.dtype), vis).reshape(lead)
         if x.dtype not in (torch.float32, torch.float64):
             raise TypeError("ReprojectionError evaluates in float32 (or float64, built from float64 observations)")
+        if use64:
+            flavour = (_F64_LARGE if self.float64_large_gradients else True) if self.float64_derivatives else False
+        else:
+            flavour = _F32_LARGE if self.large_derivatives else False
         err = _NativeObjective.apply(x, obs, vis, self.num_views, self.num_points, self.distortion, self.residual,
-                                     (_F64_LARGE if self.float64_large_gradients else True)
-                                     if (self.float64_derivatives and use64) else False)
+                                     flavour)
         return err.reshape(lead)
 
 
@@ -242,9 +253,11 @@ class RayAngleError(ReprojectionError):
     residual = native_ops.N.DAVA_RESIDUAL_RAY_ANGLE
 
     def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int,
-                 float64_derivatives: bool = False, float64_large_gradients: bool = False):
+                 float64_derivatives: bool = False, float64_large_gradients: bool = False,
+                 large_derivatives: bool = False):
         super().__init__(observations, visibility, num_views, num_points, distortion=False,
-                         float64_derivatives=float64_derivatives, float64_large_gradients=float64_large_gradients)
+                         float64_derivatives=float64_derivatives, float64_large_gradients=float64_large_gradients,
+                         large_derivatives=large_derivatives)
 
     def _torch_objective(self, x, obs, vis):
         from ..geometry.closure_ops import ray_angle_objective

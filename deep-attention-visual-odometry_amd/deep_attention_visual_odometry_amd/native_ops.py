@@ -71,15 +71,43 @@ def ba_second_order(x: torch.Tensor, observations: torch.Tensor, visibility: tor
     """(E, dE/dx, H v + (d2E/dx dobs) u, dE/dobs, (d2E/dobs dx) v + (d2E/dobs2) u) for a (B, P) fp32 batch
     (``torch.ops.dava.ba_second_order``).  ``direction`` / ``obs_direction`` None mean v = 0 / u = 0 (with both
     None only E, dE/dx and dE/dobs are meaningful)."""
+    return _second_order_f32(torch.ops.dava.ba_second_order, x, observations, visibility, num_views, num_points,
+                             distortion, direction, residual, want_hv, want_obs, obs_direction)
+
+
+def _second_order_f32(op, x, observations, visibility, num_views, num_points, distortion, direction, residual,
+                      want_hv, want_obs, obs_direction):
     x = _fp32_on_device(x, "x")
     obs, vis = _scene_inputs(x, observations, visibility)
     if obs_direction is not None:
         obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=torch.float32)).reshape(obs.shape)
-    err, grad, hv, obs_grad, obs_hv = torch.ops.dava.ba_second_order(
+    err, grad, hv, obs_grad, obs_hv = op(
         x, obs, vis, num_views, num_points, bool(distortion), _opt(direction), int(residual), bool(want_hv),
         bool(want_obs), obs_direction)
     return (err, grad, hv if want_hv else None, obs_grad if want_obs else None,
             obs_hv if (want_obs and want_hv) else None)
+
+
+def second_order_form(batch: int, num_views: int, num_points: int, distortion: bool,
+                      residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_second_order_form`` (host-only): the form the float32 second derivatives take for this scene -- 0
+    the whole dual image in LDS (``dava_ba_second_order_obs``'s launch), 1 the scene read in place and the dual
+    dE/dobs in a workspace, 2 the dual x and gradient there too -- or a negative value where they do not run."""
+    sc = scene_struct(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
+    return int(N.load_library().dava_ba_second_order_form(sc))
+
+
+def ba_second_order_large(x: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
+                          num_points: int, distortion: bool = False, direction: Optional[torch.Tensor] = None,
+                          residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, want_hv: bool = True,
+                          want_obs: bool = True, obs_direction: Optional[torch.Tensor] = None):
+    """:func:`ba_second_order` for a scene of any size: ``torch.ops.dava.ba_second_order_large`` where
+    ``dava_ba_second_order_obs`` refuses the scene (its dual image does not fit LDS) or under the F32_DUAL_FORM
+    override, else that operator itself."""
+    form0 = _ops.f32_old_symbol_runs(lambda: second_order_form(1, num_views, num_points, distortion, residual) == 0)
+    op = torch.ops.dava.ba_second_order if form0 else torch.ops.dava.ba_second_order_large
+    return _second_order_f32(op, x, observations, visibility, num_views, num_points, distortion, direction, residual,
+                             want_hv, want_obs, obs_direction)
 
 
 def _f64_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
@@ -291,16 +319,45 @@ def ba_sgd_solve_differentiable(x0: torch.Tensor, observations: torch.Tensor, vi
     """The fused gradient descent as an autograd node w.r.t. x0 and the observations: the recording launch, and
     the adjoint kernel as its backward (``torch.ops.dava.ba_sgd_solve_differentiable``).  Returns (x, errors |
     None); the errors carry no graph."""
+    return _sgd_differentiable(torch.ops.dava.ba_sgd_solve_differentiable, x0, observations, visibility, num_views,
+                               num_points, distortion, learning_rate, iterations, residual, want_errors)
+
+
+def _sgd_differentiable(op, x0, observations, visibility, num_views, num_points, distortion, learning_rate,
+                        iterations, residual, want_errors):
     N.require_device_tensor(x0, "parameters")
     if x0.dtype != torch.float32:
         raise TypeError("the fused BA kernels compute in float32 (the reference's BA dtype)")
     dev = x0.device
     obs = _c(observations.to(device=dev, dtype=torch.float32))  # (kept in the graph)
     vis = _c(visibility.detach().to(device=dev, dtype=torch.uint8))
-    x, errs, _ = torch.ops.dava.ba_sgd_solve_differentiable(
+    x, errs, _ = op(
         _c(x0), obs, vis, int(num_views), int(num_points), bool(distortion), float(learning_rate), int(iterations),
         int(residual), bool(want_errors))
     return x, (errs.detach() if want_errors else None)
+
+
+def sgd_backward_form(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+                      residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_sgd_backward_form`` (host-only): the form the descent's adjoint takes for this scene -- 0
+    ``dava_ba_sgd_backward``'s launch, 1 the scene read in place and the step's dual dE/dobs in a workspace, 2 the
+    dual x and gradient there too -- or a negative value where it does not run."""
+    return _sgd_query("dava_ba_sgd_backward_form", batch, num_views, num_points, distortion, iterations, residual)
+
+
+def ba_sgd_solve_differentiable_large(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor,
+                                      num_views: int, num_points: int, distortion: bool, *, learning_rate: float,
+                                      iterations: int, residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION,
+                                      want_errors: bool = False):
+    """:func:`ba_sgd_solve_differentiable` for any scene the recording descent runs:
+    ``torch.ops.dava.ba_sgd_solve_differentiable_large`` where ``dava_ba_sgd_backward`` refuses the scene (its dual
+    image does not fit LDS) or under the F32_DUAL_FORM override, else that operator itself.  Under
+    ``torch.compile`` tracing (which asks the library nothing) the large operator."""
+    form0 = not torch.compiler.is_compiling() and _ops.f32_old_symbol_runs(
+        lambda: sgd_backward_form(1, num_views, num_points, distortion, iterations, residual) == 0)
+    op = torch.ops.dava.ba_sgd_solve_differentiable if form0 else torch.ops.dava.ba_sgd_solve_differentiable_large
+    return _sgd_differentiable(op, x0, observations, visibility, num_views, num_points, distortion, learning_rate,
+                               iterations, residual, want_errors)
 
 
 def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,

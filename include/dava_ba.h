@@ -659,12 +659,53 @@ int dava_bfgs_update_inverse_hessian_backward_large_f64(int64_t batch, int64_t n
                                                         double* grad_s, double* grad_y, void* workspace,
                                                         size_t workspace_bytes, void* stream);
 
+/* ---- float32 second derivatives and the descent's adjoint beyond the LDS image ----
+ * dava_ba_second_order(_obs) and dava_ba_sgd_backward keep one problem's whole dual-number image in LDS and stay
+ * DAVA_ERR_UNSUPPORTED past 160 KiB (at M = 2 from N of about 1,650; C5, 16 x 4096).  The entry points below run
+ * the same kernel bodies in the forms of the float64 ones above:
+ *   0  the launch of the old symbol (no workspace);
+ *   1  the dual x and gradient in LDS (16 Pv bytes, Pv = round_up(P, 4)), the scene read in place, the dual dE/dobs
+ *      in a workspace of B * 4MN floats -- formed only when an observation output is asked for;
+ *   2  the dual x and gradient in a per-problem workspace slice of 4 Pv floats too (C5: 16 Pv = 198 KB does not
+ *      fit LDS).
+ * Workspace: [dual dE/dobs: B * 4MN floats, only with an observation output | form 2: B * 4 Pv floats | a 256-byte
+ * tail], uninitialised device memory; nothing is read from it before it is written.  The form is the lowest whose
+ * image fits; the F32_DUAL_FORM override (1 | 2) raises it, never lowers it.  Results are bitwise those of form 0
+ * wherever more than one form runs.  No atomics: two launches give the same bits.
+ *
+ * dava_ba_second_order_form (host-only): 0, 1, 2 or minus the status.
+ * dava_ba_second_order_large_workspace_bytes (host-only): obs_outputs != 0 when obs_grad_out or obs_hv_out will be
+ *   asked for; includes the tail; 0 only where no form runs (or the scene is invalid).
+ * dava_ba_second_order_large: dava_ba_second_order_obs's contract and outputs at any form.  Checks, all before a
+ *   launch: the scene; an empty batch is DAVA_OK; NULL x is DAVA_ERR_INVALID_ARGUMENT; a shape no form runs is
+ *   DAVA_ERR_UNSUPPORTED; a form that needs workspace with none or too little is DAVA_ERR_WORKSPACE. */
+int dava_ba_second_order_form(const DavaScene* scene);
+size_t dava_ba_second_order_large_workspace_bytes(const DavaScene* scene, int obs_outputs);
+int dava_ba_second_order_large(const DavaScene* scene, const float* x, const float* direction,
+                               const float* obs_direction, float* error_out, float* grad_out, float* hv_out,
+                               float* obs_grad_out, float* obs_hv_out, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
+/* The adjoint of the fused gradient descent (dava_ba_sgd_backward's contract, tape and outputs) at any form.  In
+ * forms 1 and 2 the dual dE/dobs of one step lives in the workspace (only when observations_grad is non-NULL) and
+ * the accumulator of dL/dobs is observations_grad itself, zeroed and updated once per step by the thread that owns
+ * the element, in form 0's arithmetic and order.  The tape is dava_ba_sgd_solve_record's, which runs these scenes
+ * already.  dava_ba_sgd_backward_form (host-only): 0, 1, 2 or minus the status (the adjoint's own fit, whatever
+ * the forward takes).  The workspace query takes whether observations_grad will be asked for.  Checks of the
+ * launch, in order: the scene; the config; an empty batch is DAVA_OK; NULL x_out_grad or x0_grad is
+ * DAVA_ERR_INVALID_ARGUMENT; DAVA_ERR_UNSUPPORTED; a missing or short tape or workspace is DAVA_ERR_WORKSPACE. */
+int dava_ba_sgd_backward_form(const DavaScene* scene, const DavaSgdConfig* config);
+size_t dava_ba_sgd_backward_large_workspace_bytes(const DavaScene* scene, const DavaSgdConfig* config, int obs_grad);
+int dava_ba_sgd_backward_large(const DavaScene* scene, const DavaSgdConfig* config, const void* tape,
+                               size_t tape_bytes, const float* x_out_grad, float* x0_grad, float* observations_grad,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- test and A/B hooks ----
  * The library makes its launch choices itself (LDS or global-vector mode, waves per workgroup,
  * on-chip history entries, work queue, ...) and reads NOTHING from the environment.  Tests and A/B
  * measurements override a choice by name (FORCE_GV, GV_NO_XL, SOLVE_WAVES, WG_PER_CU, LDS_HISTORY,
  * STAGGER, STAGGER_LEVELS, NO_PPT, NO_QUEUE, ADJ_GV_WAVES, ADJ_FORCE_GV, ADJ_LDS_ENTRIES, ADJ_GD_HBM,
- * COMPACT_SWITCH, GV_SCALAR_SLICE, ADJ_SC_GLOBAL, F64_FORM; csrc/dava_debug.hpp); value < 0 restores the
+ * COMPACT_SWITCH, GV_SCALAR_SLICE, ADJ_SC_GLOBAL, F64_FORM, F32_DUAL_FORM; csrc/dava_debug.hpp); value < 0 restores the
  * library's choice.  Process-wide, not thread-safe, host-only.  DAVA_ERR_INVALID_ARGUMENT for an
  * unknown name.                                                                                   */
 int dava_debug_set_override(const char* name, int64_t value);

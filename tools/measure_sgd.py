@@ -13,7 +13,14 @@ times are HIP events around the calls, ended by a device synchronise.  For C3 th
 the fused forward to K x 108.04 us, the time of one C3 evaluation sweep alone at B = 8192
 (profiles/r05_eval_summary.json).  Needs a ROCm device: there is no fallback.
 
+--mode large: descent + gradient (the recording launch, then the adjoint for d (w . x_K) / d x0 and / d obs) where
+only forms 1 and 2 of the adjoint run -- C5 (16 x 4096, B = 256: form 2) and a two-view scene with 1,800 points
+(B = 1024: form 1), K = 100, lr = 1e-5 -- next to the fused forward alone (nothing else on the GPU computes these
+gradients); and at C3 (B = 8192) the adjoint in form 0 and raised to forms 1 and 2 through the F32_DUAL_FORM
+override, alternated run by run.  Lines are appended to profiles/sgd_large.jsonl.
+
 usage: python tools/measure_sgd.py [--out FILE] [--repeats 5] [--configs c2:1024,c3:8192] [--iterations 100]
+       python tools/measure_sgd.py --mode large [--out FILE] [--repeats 5] [--iterations 100]
 """
 import argparse
 import json
@@ -25,7 +32,8 @@ sys.path[:0] = [REPO, os.path.join(REPO, "deep-attention-visual-odometry_amd")]
 
 import torch  # noqa: E402
 
-SHAPES = {"c1": (2, 64, False), "c2": (2, 128, False), "c3": (4, 256, True)}
+SHAPES = {"c1": (2, 64, False), "c2": (2, 128, False), "c3": (4, 256, True), "c5": (16, 4096, False),
+          "2x1800": (2, 1800, False)}
 C3_SWEEP_US = 108.04  # profiles/r05_eval_summary.json, B = 8192
 
 
@@ -106,17 +114,82 @@ def measure(shape, b, k, lr, repeats, dev):
     return rec
 
 
+def measure_large(shape, b, k, lr, repeats, forms, dev):
+    """Descent + gradient with the adjoint in each of `forms` (None: the form the fit chooses; 1 | 2: raised through
+    F32_DUAL_FORM), alternated run by run, and the fused forward alone."""
+    from deep_attention_visual_odometry_amd import _native as N
+    from deep_attention_visual_odometry_amd import make_scenes, native_ops
+
+    m, n, dist = SHAPES[shape]
+    s = make_scenes(b, m, n, distortion=dist, seed=7, drop=0.0 if dist else 0.1)
+    x0 = torch.tensor(s.initial, device=dev)
+    obs = torch.tensor(s.observations, device=dev)
+    vis = torch.tensor(s.visibility, device=dev).to(torch.uint8)
+    w = torch.randn(x0.shape, generator=torch.Generator().manual_seed(3)).to(dev)
+
+    def forward():
+        return native_ops.ba_sgd_solve(x0, obs, vis, m, n, dist, learning_rate=lr, iterations=k)[0]
+
+    def gradient(forced):
+        with N.debug_overrides(**({} if forced is None else {"F32_DUAL_FORM": forced})):
+            xg, og = x0.clone().requires_grad_(True), obs.clone().requires_grad_(True)
+            out, _ = native_ops.ba_sgd_solve_differentiable_large(xg, og, vis, m, n, dist, learning_rate=lr,
+                                                                  iterations=k)
+            gx, go = torch.autograd.grad((out * w).sum(), [xg, og])
+        return gx, go
+
+    paths = {"forward": forward}
+    paths.update({f"gradient_form_{'fit' if f is None else f}": (lambda f=f: gradient(f)) for f in forms})
+    best = {name: float("inf") for name in paths}
+    outs = {name: timed(fn, dev)[1] for name, fn in paths.items()}  # warm-up: code objects, allocator
+    for rep in range(repeats):
+        for name in (list(paths) if rep % 2 == 0 else list(paths)[::-1]):  # both orders
+            best[name] = min(best[name], timed(paths[name], dev)[0])
+    rec = {"mode": "large", "shape": shape, "B": b, "K": k, "learning_rate": lr, "P": x0.shape[1], "repeats": repeats,
+           "adjoint_form_by_fit": native_ops.sgd_backward_form(b, m, n, dist, k)}
+    for name, ms in best.items():
+        rec[name + "_ms"] = round(ms, 3)
+        rec[name + "_problems_per_s"] = round(b / (ms * 1e-3), 1)
+        if name != "forward":
+            rec[name + "_over_forward"] = round(ms / best["forward"], 2)
+            gx, go = outs[name]
+            rec[name + "_finite_rows"] = int((torch.isfinite(gx).all(dim=-1) & torch.isfinite(go.flatten(1)).all(dim=-1)).sum())
+    first = next(name for name in paths if name != "forward")
+    for name in paths:  # the forms compute the same bits
+        if name not in ("forward", first):
+            rec[name + "_bitwise_" + first] = bool(
+                torch.equal(outs[name][0].nan_to_num(), outs[first][0].nan_to_num())
+                and torch.equal(outs[name][1].nan_to_num(), outs[first][1].nan_to_num()))
+    return rec
+
+
+def main_large(args, dev):
+    out = args.out or os.path.join(REPO, "profiles", "sgd_large.jsonl")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lr = 1e-5 if args.learning_rate is None else args.learning_rate
+    for shape, b, forms in (("c3", 8192, (None, 1, 2)), ("2x1800", 1024, (None, 2)), ("c5", 256, (None,))):
+        rec = measure_large(shape, b, args.iterations, lr, max(args.repeats, 5), forms, dev)
+        print(json.dumps(rec), flush=True)
+        with open(out, "a") as fh:
+            fh.write(json.dumps(rec) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "sgd_solve.jsonl"))
+    ap.add_argument("--mode", choices=("solve", "large"), default="solve")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--configs", default="c2:1024,c3:8192")
     ap.add_argument("--iterations", type=int, default=100)
-    ap.add_argument("--learning-rate", type=float, default=1e-4)
+    ap.add_argument("--learning-rate", type=float, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("measure_sgd.py needs a ROCm device: nothing is measured without one")
     dev = torch.device("cuda", 0)
+    if args.mode == "large":
+        return main_large(args, dev)
+    args.out = args.out or os.path.join(REPO, "profiles", "sgd_solve.jsonl")
+    args.learning_rate = 1e-4 if args.learning_rate is None else args.learning_rate
     lines = []
     for config in args.configs.split(","):
         shape, b = config.split(":")
