@@ -14,16 +14,12 @@
 // Workspace: [dual dE/dobs B x 4MN, if an observation output is asked for | form 2: B x 4 Pv | 256-byte tail].
 // The host side is one plan and one launcher for the two entry points (the conventions of dava_f64.hpp):
 // dava_ba_second_order_f64 plans with any_form = false, dava_ba_second_order_large_f64 and the queries with true.
-#include "ba_objective.hpp"
-#include "dava_debug.hpp"
-#include "dava_f64.hpp"
+#include "ba_second_carve_f64.hpp"
 
 #include <type_traits>
 
 namespace dava {
 namespace f64 {
-
-using Dual64 = DualT<double>;
 
 struct SecondArgs {
   Layout L;
@@ -41,58 +37,6 @@ struct LargeSecondArgs : SecondArgs {
 
 template <int FORM>
 using second_args_t = std::conditional_t<FORM != 0, LargeSecondArgs, SecondArgs>;
-
-struct SecondCarve {
-  int x, g, views, vpart, obsd, scratch, obs, vis_bytes_off;  // offsets in doubles
-  long long total_bytes;
-};
-
-__host__ __device__ inline SecondCarve carve_second(int M, int N, int Pv) {
-  SecondCarve c{};
-  const long long MN = (long long)M * N;
-  const long long doubles = 4LL * Pv + 2LL * views_floats(M) + 2LL * vpart_floats(M) + 4 * MN + 2 * kWaves * 32 + 2 * MN;
-  c.total_bytes = doubles * 8 + round_up((int)(MN < (1 << 30) ? MN : (1 << 30)), 16);
-  if (c.total_bytes > kMaxLdsBytes) return c;  // (offsets are meaningful only for an image that fits)
-  int off = 0;
-  c.x = off; off += 2 * Pv;                  // Dual64
-  c.g = off; off += 2 * Pv;                  // Dual64
-  c.views = off; off += 2 * views_floats(M);  // Dual64
-  c.vpart = off; off += 2 * vpart_floats(M);  // Dual64
-  c.obsd = off; off += 4 * (int)MN;          // Dual64 dE/dobs
-  c.scratch = off; off += 2 * kWaves * 32;
-  c.obs = off; off += 2 * (int)MN;
-  c.vis_bytes_off = off * 8;
-  return c;
-}
-
-// The LDS image of forms 1 and 2: no scene, no dE/dobs and in form 2 no x / g either.  x and g are relative to
-// the vectors' base (LDS, or the problem's slice), the others to the LDS base.
-__host__ __device__ inline SecondCarve carve_second_large(int M, int Pv, int form) {
-  SecondCarve c{};
-  const long long doubles = (form == 1 ? 4LL * Pv : 0) + 2LL * views_floats(M) + 2LL * vpart_floats(M) + 2 * kWaves * 32;
-  c.total_bytes = doubles * 8;
-  if (c.total_bytes > kMaxLdsBytes) return c;
-  int off = 0;
-  c.x = off; off += 2 * Pv;
-  c.g = off; off += 2 * Pv;
-  if (form != 1) off = 0;
-  c.views = off; off += 2 * views_floats(M);
-  c.vpart = off; off += 2 * vpart_floats(M);
-  c.scratch = off; off += 2 * kWaves * 32;
-  return c;
-}
-
-// The form a scene takes: the lowest whose image fits, raised (never lowered) by the F64_FORM override; -1 where
-// not even form 2's image (the dual view constants and partials) fits.
-inline int choose_second_form(int M, int N, int Pv) {
-  int form = 2;
-  if (carve_second(M, N, Pv).total_bytes <= kMaxLdsBytes) form = 0;
-  else if (carve_second_large(M, Pv, 1).total_bytes <= kMaxLdsBytes) form = 1;
-  const long long forced = debug_knob(kDbgF64Form);
-  if ((forced == 1 || forced == 2) && forced > form) form = (int)forced;
-  if (form == 2 && carve_second_large(M, Pv, 2).total_bytes > kMaxLdsBytes) return -1;
-  return form;
-}
 
 template <int RES, int FORM = 0>
 __global__ __launch_bounds__(kBlock, 1) void ba_second_order_f64_kernel(second_args_t<FORM> a) {

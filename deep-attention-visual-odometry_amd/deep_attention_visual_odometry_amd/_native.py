@@ -115,6 +115,14 @@ class DavaSgdConfig(ctypes.Structure):
     ]
 
 
+class DavaSgdConfigF64(ctypes.Structure):
+    """The float64 fused gradient descent (`dava_ba_sgd_*_f64`): learning_rate crosses as a double, unrounded."""
+    _fields_ = [
+        ("learning_rate", ctypes.c_double),
+        ("iterations", _c_i32),
+    ]
+
+
 class DavaSolvePlan(ctypes.Structure):
     _fields_ = [
         ("global_vectors", _c_i32),
@@ -214,6 +222,20 @@ SIGNATURES = {
                                                                      ctypes.POINTER(DavaSgdConfig), ctypes.c_int]),
     "dava_ba_sgd_backward_large": (ctypes.c_int, [ctypes.POINTER(DavaScene), ctypes.POINTER(DavaSgdConfig), _vp,
                                                   ctypes.c_size_t, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    # float64 fused gradient descent and its adjoint, forms 0, 1 and 2 (csrc/sgd_solve_f64.hip, sgd_adjoint_f64.hip)
+    "dava_ba_sgd_solve_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSgdConfigF64), _vp, _vp,
+                                             _vp, _vp, ctypes.c_size_t, _vp]),
+    "dava_ba_sgd_solve_record_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSgdConfigF64),
+                                                    _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "dava_ba_sgd_tape_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSgdConfigF64)]),
+    "dava_ba_sgd_solve_form_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSgdConfigF64)]),
+    "dava_ba_sgd_solve_workspace_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                                ctypes.POINTER(DavaSgdConfigF64)]),
+    "dava_ba_sgd_backward_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSgdConfigF64), _vp,
+                                                ctypes.c_size_t, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dava_ba_sgd_backward_form_f64": (ctypes.c_int, [ctypes.POINTER(DavaSceneF64), ctypes.POINTER(DavaSgdConfigF64)]),
+    "dava_ba_sgd_backward_workspace_bytes_f64": (ctypes.c_size_t, [ctypes.POINTER(DavaSceneF64),
+                                                                   ctypes.POINTER(DavaSgdConfigF64), ctypes.c_int]),
     "dava_debug_set_override": (ctypes.c_int, [ctypes.c_char_p, _c_i64]),
     "dava_debug_clear_overrides": (None, []),
     "dava_abi_version": (ctypes.c_int, []),

@@ -1375,6 +1375,151 @@ def _(focal, cx, cy, translation, lie, world, target, visibility, minimum_z_dist
     return focal.new_empty((b, e, 3 + 6 * m + 3 * (n - 2)))
 
 
+# ---------------------------------------- float64 fused gradient descent (SGDSolver) and its adjoint
+# One operator per operation: the C symbols take forms 0, 1 and 2 themselves (csrc/sgd_solve_f64.hip,
+# sgd_adjoint_f64.hip), with a workspace from torch's allocator sized by the library's host queries.
+
+def sgd_config_f64(learning_rate: float, iterations: int) -> N.DavaSgdConfigF64:
+    return N.DavaSgdConfigF64(float(learning_rate), int(iterations))
+
+
+def _sgd_scene_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
+                   distortion: bool, learning_rate: float, iterations: int, residual: int, what: str):
+    _require_float64(x0, what)
+    _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
+    if iterations < 0:
+        raise ValueError(f"iterations must be >= 0, got {iterations}")
+    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, x0.shape[0], residual)
+    return sc, sgd_config_f64(learning_rate, iterations)
+
+
+_SGD_REFUSAL_F64 = ("this scene has no float64 fused gradient descent: more views than the view constants can hold "
+                    "in one workgroup's 160 KiB of LDS")
+_SGD_ADJOINT_REFUSAL_F64 = ("this scene has no float64 fused adjoint of the gradient descent: more views than the "
+                            "dual view constants can hold in one workgroup's 160 KiB of LDS")
+
+
+def _sgd_solve_workspace_f64(lib, sc, cfg, dev):
+    """(tensor, pointer, bytes) of the descent's workspace: form 2's vectors, or (None, None, 0)."""
+    if lib.dava_ba_sgd_solve_form_f64(sc, cfg) < 0:
+        raise ValueError(_SGD_REFUSAL_F64)
+    need = int(lib.dava_ba_sgd_solve_workspace_bytes_f64(sc, cfg))
+    if need == 0:
+        return None, None, 0
+    ws = _scratch(need, dev)
+    return ws, N.ptr(ws), ws.numel()
+
+
+@torch.library.custom_op("dava::ba_sgd_solve_f64", mutates_args=(), device_types=_CUDA)
+def ba_sgd_solve_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
+                     distortion: bool, learning_rate: float, iterations: int, residual: int,
+                     want_errors: bool) -> Tuple[Tensor, Tensor]:
+    """``dava_ba_sgd_solve_f64``: ``iterations`` steps x <- x - learning_rate dE/dx of a (B, P) float64 batch in
+    one launch, at any form.  Returns (x, E(x_k) (B, iterations) or empty)."""
+    lib = N.load_library()
+    sc, cfg = _sgd_scene_f64(x0, observations, visibility, num_views, num_points, distortion, learning_rate,
+                             iterations, residual, "the float64 fused gradient descent")
+    b, dev = x0.shape[0], x0.device
+    _ws, ws_ptr, ws_bytes = _sgd_solve_workspace_f64(lib, sc, cfg, dev)
+    x_out = torch.empty_like(x0)
+    errs = torch.empty((b, iterations), device=dev, dtype=torch.float64) if want_errors else _empty0(x0)
+    with torch.cuda.device(dev):
+        N.check(lib.dava_ba_sgd_solve_f64(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
+                                          ws_ptr, ws_bytes, N.stream_of(dev)), "dava_ba_sgd_solve_f64")
+    return x_out, errs
+
+
+@ba_sgd_solve_f64.register_fake
+def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
+      want_errors):
+    return torch.empty_like(x0), x0.new_empty((x0.shape[0], iterations) if want_errors else (0,))
+
+
+@torch.library.custom_op("dava::ba_sgd_solve_differentiable_f64", mutates_args=(), device_types=_CUDA)
+def ba_sgd_solve_differentiable_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
+                                    num_points: int, distortion: bool, learning_rate: float, iterations: int,
+                                    residual: int, want_errors: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """``dava_ba_sgd_solve_record_f64``: ``ba_sgd_solve_f64`` (bitwise its x and errors) that also writes the tape
+    (B, iterations, round_up(P, 4)) of x_k in float64.  An autograd node w.r.t. x0 and the observations: its backward
+    is ``ba_sgd_backward_f64`` (not differentiable twice).  Returns (x, errors or empty, tape)."""
+    lib = N.load_library()
+    sc, cfg = _sgd_scene_f64(x0, observations, visibility, num_views, num_points, distortion, learning_rate,
+                             iterations, residual, "the float64 recording gradient descent")
+    if lib.dava_ba_sgd_backward_form_f64(sc, cfg) < 0:
+        raise ValueError(_SGD_ADJOINT_REFUSAL_F64)
+    b, dev = x0.shape[0], x0.device
+    _ws, ws_ptr, ws_bytes = _sgd_solve_workspace_f64(lib, sc, cfg, dev)
+    tape = torch.empty((b, iterations, sgd_tape_rows(x0.shape[1])), device=dev, dtype=torch.float64)
+    if _POISON:
+        tape.fill_(float("nan"))
+    x_out = torch.empty_like(x0)
+    errs = torch.empty((b, iterations), device=dev, dtype=torch.float64) if want_errors else _empty0(x0)
+    with torch.cuda.device(dev):
+        N.check(lib.dava_ba_sgd_solve_record_f64(sc, cfg, N.ptr(x0), N.ptr(x_out),
+                                                 N.ptr(errs) if want_errors else None,
+                                                 N.ptr(tape) if tape.numel() else None, tape.numel() * 8, ws_ptr,
+                                                 ws_bytes, N.stream_of(dev)), "dava_ba_sgd_solve_record_f64")
+    return x_out, errs, tape
+
+
+@ba_sgd_solve_differentiable_f64.register_fake
+def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
+      want_errors):
+    b = x0.shape[0]
+    return (torch.empty_like(x0), x0.new_empty((b, iterations) if want_errors else (0,)),
+            x0.new_empty((b, iterations, sgd_tape_rows(x0.shape[1]))))
+
+
+@torch.library.custom_op("dava::ba_sgd_backward_f64", mutates_args=(), device_types=_CUDA)
+def ba_sgd_backward_f64(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
+                        num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int,
+                        want_observations: bool) -> Tuple[Tensor, Tensor]:
+    """``dava_ba_sgd_backward_f64``: (dL/dx0, dL/dobs or empty) of a recorded float64 descent for dL/dx_out."""
+    lib = N.load_library()
+    sc, cfg = _sgd_scene_f64(x_out_grad, observations, visibility, num_views, num_points, distortion, learning_rate,
+                             iterations, residual, "the float64 gradient descent's adjoint")
+    b, dev = x_out_grad.shape[0], x_out_grad.device
+    rows = sgd_tape_rows(x_out_grad.shape[1])
+    # (the kernel dereferences the tape as device memory of this launch: refuse anything else loudly)
+    if (tape.device != dev or tape.dtype != torch.float64 or not tape.is_contiguous()
+            or tuple(tape.shape) != (b, iterations, rows)):
+        raise ValueError(f"tape must be the recording call's contiguous float64 ({b}, {iterations}, {rows}) tensor "
+                         f"on {dev}, got {tuple(tape.shape)} {tape.dtype} on {tape.device}")
+    if lib.dava_ba_sgd_backward_form_f64(sc, cfg) < 0:
+        raise ValueError(_SGD_ADJOINT_REFUSAL_F64)
+    need = int(lib.dava_ba_sgd_backward_workspace_bytes_f64(sc, cfg, 1 if want_observations else 0))
+    ws = _scratch(need, dev) if need else None
+    gx = torch.empty_like(x_out_grad)
+    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
+    with torch.cuda.device(dev):
+        N.check(lib.dava_ba_sgd_backward_f64(sc, cfg, N.ptr(tape) if tape.numel() else None, tape.numel() * 8,
+                                             N.ptr(x_out_grad), N.ptr(gx),
+                                             N.ptr(gobs) if want_observations else None, N.ptr(ws),
+                                             ws.numel() if need else 0, N.stream_of(dev)),
+                "dava_ba_sgd_backward_f64")
+    return gx, gobs
+
+
+@ba_sgd_backward_f64.register_fake
+def _(x_out_grad, tape, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+      residual, want_observations):
+    return (torch.empty_like(x_out_grad),
+            torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
+
+
+@torch.autograd.function.once_differentiable
+def _sgd_backward_f64(ctx, x_grad, _errors_grad, _tape_grad):
+    tape, observations, visibility = ctx.saved_tensors
+    need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    x_grad = x_grad.to(torch.float64)
+    gx, gobs = ba_sgd_backward_f64(x_grad if x_grad.is_contiguous() else x_grad.contiguous(), tape,
+                                   observations.detach(), visibility, *ctx.meta, bool(need_obs))
+    return (gx if need_x else None, gobs if need_obs else None) + (None,) * 8
+
+
+ba_sgd_solve_differentiable_f64.register_autograd(_sgd_backward_f64, setup_context=_sgd_setup_context)
+
+
 OPS = ("bfgs_solve", "ba_solve", "ba_solve_record", "ba_solve_backward", "ba_evaluate", "ba_second_order",
        "ba_second_order_f64", "ba_solve_record_f64", "ba_solve_backward_f64", "ba_second_order_large_f64",
        "ba_solve_record_large_f64", "ba_solve_backward_large_f64", "bfgs_update_inverse_hessian",
@@ -1382,4 +1527,5 @@ OPS = ("bfgs_solve", "ba_solve", "ba_solve_record", "ba_solve_backward", "ba_eva
        "bfgs_scale_matrix", "bfgs_scale_matrix_backward", "bfgs_search_direction", "bfgs_search_direction_backward",
        "wolfe_init", "wolfe_propose", "wolfe_update", "l1_camera_evaluate", "l1_camera_vjp",
        "ba_sgd_solve", "ba_sgd_solve_differentiable", "ba_sgd_backward", "ba_second_order_large",
-       "ba_sgd_solve_differentiable_large", "ba_sgd_backward_large")
+       "ba_sgd_solve_differentiable_large", "ba_sgd_backward_large", "ba_sgd_solve_f64",
+       "ba_sgd_solve_differentiable_f64", "ba_sgd_backward_f64")

@@ -4,7 +4,7 @@
 
 with the reference's two constructor keywords and its ``forward(parameters, error_function)`` contract:
 ``error_function`` takes ONE argument, there is no stopping rule, no mask and no training-mode behaviour, and the
-output requires grad iff the input does.  Three execution paths:
+output requires grad iff the input does.  Four execution paths:
 
 1. **Fused** -- ``error_function`` is a :class:`ReprojectionError` or :class:`RayAngleError` and the parameters
    are float32 on the device: the whole descent is ONE launch of ``dava_ba_sgd_solve`` (include/dava_ba.h), one
@@ -15,12 +15,17 @@ output requires grad iff the input does.  Three execution paths:
    ``dava_ba_sgd_backward_supported``.  An objective built with ``large_derivatives=True`` takes it at every scene
    the recording descent and some form of the adjoint run (``dava_ba_sgd_backward_large``: forms 1 and 2 beyond the
    LDS image, C5 among them).
-3. **The reference's loop** in torch, with ``error_function(parameters)`` and ``torch.autograd.grad(...,
-   create_graph=...)`` -- any closure, CPU tensors, float64, and a fused objective whose image the fused kernels
-   do not take (there the objective is an ordinary closure on its own kernels).
+3. **Fused, float64** -- the objective was built with ``float64_descent=True`` (from float64 device observations)
+   and the parameters are float64 on the device: ONE launch of ``dava_ba_sgd_solve_f64`` wherever
+   ``dava_ba_sgd_solve_form_f64`` >= 0; with ``parameters.requires_grad`` the recording launch
+   (``dava_ba_sgd_solve_record_f64``) and the adjoint kernel (``dava_ba_sgd_backward_f64``) wherever both form
+   queries are >= 0.  Each operation takes form 0, 1 or 2 by its own fit, so C5 runs fused in both directions.
+4. **The reference's loop** in torch, with ``error_function(parameters)`` and ``torch.autograd.grad(...,
+   create_graph=...)`` -- any closure, CPU tensors, float64 without ``float64_descent``, and a fused objective
+   whose image the fused kernels do not take (there the objective is an ordinary closure on its own kernels).
 
 Nothing falls back from the GPU to the CPU.  ``last_errors`` holds E(x_k), k = 0 .. iterations-1, shaped
-(B..., iterations), after a fused call and ``None`` otherwise.
+(B..., iterations), after a fused call (float64 after a float64 one) and ``None`` otherwise.
 """
 from typing import Callable, Optional
 
@@ -57,14 +62,27 @@ class SGDSolver(Module):
             elif torch.compiler.is_compiling() or native_ops.sgd_backward_supported(*shape, self.iterations,
                                                                                     error_function.residual):
                 return self._fused(parameters, error_function, native_ops.ba_sgd_solve_differentiable)
+        elif (isinstance(error_function, ReprojectionError) and error_function.float64_descent
+                and parameters.device.type == "cuda" and parameters.dtype == torch.float64 and self.iterations >= 0):
+            batch = max(parameters.numel() // max(parameters.size(-1), 1), 1)
+            query = (batch, error_function.num_views, error_function.num_points, error_function.distortion,
+                     self.iterations, error_function.residual)
+            if not parameters.requires_grad:
+                if torch.compiler.is_compiling() or native_ops.sgd_solve_form_f64(*query) >= 0:
+                    return self._fused(parameters, error_function, native_ops.ba_sgd_solve_f64, float64=True)
+            elif torch.compiler.is_compiling() or (native_ops.sgd_solve_form_f64(*query) >= 0
+                                                   and native_ops.sgd_backward_form_f64(*query) >= 0):
+                return self._fused(parameters, error_function, native_ops.ba_sgd_solve_differentiable_f64,
+                                   float64=True)
         return self._loop(parameters, error_function)
 
-    def _fused(self, parameters, fn: ReprojectionError, solve):
+    def _fused(self, parameters, fn: ReprojectionError, solve, float64: bool = False):
         lead = parameters.shape[:-1]
         if fn.batch_shape != lead:
             raise ValueError(f"ReprojectionError batch shape {tuple(fn.batch_shape)} != parameters {tuple(lead)}")
+        observations = fn.observations64 if float64 else fn.observations
         x, errors = solve(parameters.reshape(-1, parameters.size(-1)),
-                          fn.observations.reshape(-1, fn.num_views, fn.num_points, 2),
+                          observations.reshape(-1, fn.num_views, fn.num_points, 2),
                           fn.visibility.reshape(-1, fn.num_views, fn.num_points), fn.num_views, fn.num_points,
                           fn.distortion, learning_rate=self.learning_rate, iterations=self.iterations,
                           residual=fn.residual, want_errors=True)

@@ -150,14 +150,19 @@ class ReprojectionError:
     ``large_derivatives=True`` (independent of the float64 keywords) does the same for float32 parameters: the
     float32 second derivatives -- create_graph, observations that require grad, the double backward of dE/dobs --
     run at any admitted scene size (``dava_ba_second_order_large``), and ``SGDSolver`` differentiates through its
-    fused descent there; without it such scenes keep raising ``RuntimeError``.  With ``distortion=True`` the
-    five Brown-Conrady coefficients (k1 k2 k3 p1 p2) are appended to the
+    fused descent there; without it such scenes keep raising ``RuntimeError``.
+    ``float64_descent=True`` (independent of the other keywords; float64 device observations required, else
+    ``ValueError``) makes ``SGDSolver`` run float64 parameters as the fused float64 descent
+    (``dava_ba_sgd_solve_f64``) and, with ``requires_grad``, its recording launch and adjoint kernel, at every
+    scene size their forms take; without it a float64 ``SGDSolver`` call keeps the torch loop.
+    With ``distortion=True`` the five Brown-Conrady coefficients (k1 k2 k3 p1 p2) are appended to the
     parameter vector (``camera_model/distorted_camera_model.py:59-86``).
     """
 
     def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int,
                  distortion: bool = False, float64_derivatives: bool = False,
-                 float64_large_gradients: bool = False, large_derivatives: bool = False):
+                 float64_large_gradients: bool = False, large_derivatives: bool = False,
+                 float64_descent: bool = False):
         if observations.shape[-3:] != (num_views, num_points, 2):
             raise ValueError(f"observations must end in ({num_views}, {num_points}, 2), got {tuple(observations.shape)}")
         if visibility.shape != observations.shape[:-1]:
@@ -182,6 +187,11 @@ class ReprojectionError:
             raise ValueError("float64_large_gradients=True needs float64_derivatives=True")
         # opt-in: float32 second derivatives (and SGDSolver's adjoint) for scenes beyond the LDS image
         self.large_derivatives = bool(large_derivatives)
+        # opt-in: SGDSolver runs float64 parameters as the fused float64 descent (and its adjoint)
+        self.float64_descent = bool(float64_descent)
+        if self.float64_descent and self.observations64 is None:
+            raise ValueError("float64_descent=True needs float64 observations on a ROCm device "
+                             f"(got {observations.dtype} on {observations.device})")
         self.visibility = visibility.to(torch.uint8)
         self.num_views = int(num_views)
         self.num_points = int(num_points)
@@ -254,10 +264,10 @@ class RayAngleError(ReprojectionError):
 
     def __init__(self, observations: torch.Tensor, visibility: torch.Tensor, num_views: int, num_points: int,
                  float64_derivatives: bool = False, float64_large_gradients: bool = False,
-                 large_derivatives: bool = False):
+                 large_derivatives: bool = False, float64_descent: bool = False):
         super().__init__(observations, visibility, num_views, num_points, distortion=False,
                          float64_derivatives=float64_derivatives, float64_large_gradients=float64_large_gradients,
-                         large_derivatives=large_derivatives)
+                         large_derivatives=large_derivatives, float64_descent=float64_descent)
 
     def _torch_objective(self, x, obs, vis):
         from ..geometry.closure_ops import ray_angle_objective

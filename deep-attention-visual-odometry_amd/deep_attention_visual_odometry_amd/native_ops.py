@@ -360,6 +360,83 @@ def ba_sgd_solve_differentiable_large(x0: torch.Tensor, observations: torch.Tens
                                iterations, residual, want_errors)
 
 
+def _sgd_query_f64(name: str, batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+                   residual: int, *more) -> int:
+    sc = _ops.scene_struct_f64(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
+    return int(getattr(N.load_library(), name)(sc, _ops.sgd_config_f64(0.0, iterations), *more))
+
+
+def sgd_tape_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+                       residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_sgd_tape_bytes_f64`` (host-only): B * iterations * round_up(P, 4) * 8, or 0 where the float64 fused
+    gradient descent does not run this scene (and for ``iterations == 0``, which needs no tape)."""
+    return _sgd_query_f64("dava_ba_sgd_tape_bytes_f64", batch, num_views, num_points, distortion, iterations, residual)
+
+
+def sgd_solve_form_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1,
+                       residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_sgd_solve_form_f64`` (host-only): the form the float64 fused descent takes for this scene -- 0 the
+    whole image in LDS, 1 the scene read in place, 2 x and the gradient in the workspace too -- or a negative value
+    where it does not run."""
+    return _sgd_query_f64("dava_ba_sgd_solve_form_f64", batch, num_views, num_points, distortion, iterations, residual)
+
+
+def sgd_backward_form_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1,
+                          residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_sgd_backward_form_f64`` (host-only): the form the float64 descent's adjoint takes -- 0 the dual
+    image and the accumulator in LDS, 1 the scene read in place and the step's dual dE/dobs in a workspace, 2 the
+    dual x and gradient there too -- or a negative value where it does not run.  Independent of the descent's form."""
+    return _sgd_query_f64("dava_ba_sgd_backward_form_f64", batch, num_views, num_points, distortion, iterations,
+                          residual)
+
+
+def sgd_solve_workspace_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1,
+                                  residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
+    """``dava_ba_sgd_solve_workspace_bytes_f64`` (host-only): form 2's vectors and the tail; 0 in forms 0 and 1."""
+    return _sgd_query_f64("dava_ba_sgd_solve_workspace_bytes_f64", batch, num_views, num_points, distortion,
+                          iterations, residual)
+
+
+def sgd_backward_workspace_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool,
+                                     iterations: int = 1, residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION,
+                                     observations_grad: bool = True) -> int:
+    """``dava_ba_sgd_backward_workspace_bytes_f64`` (host-only)."""
+    return _sgd_query_f64("dava_ba_sgd_backward_workspace_bytes_f64", batch, num_views, num_points, distortion,
+                          iterations, residual, 1 if observations_grad else 0)
+
+
+def ba_sgd_solve_f64(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
+                     num_points: int, distortion: bool, *, learning_rate: float, iterations: int,
+                     residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, want_errors: bool = False):
+    """``iterations`` steps of x <- x - learning_rate dE/dx for a (B, P) float64 batch in one launch
+    (``torch.ops.dava.ba_sgd_solve_f64``), at any scene size.  Returns (x, E(x_k) (B, iterations) | None).  No
+    graph.  A float32 tensor raises ``TypeError``."""
+    x0 = _f64_on_device(x0, "parameters")
+    obs, vis = _scene_inputs(x0, observations, visibility)
+    x, errs = torch.ops.dava.ba_sgd_solve_f64(x0, obs, vis, int(num_views), int(num_points), bool(distortion),
+                                              float(learning_rate), int(iterations), int(residual), bool(want_errors))
+    return x, (errs if want_errors else None)
+
+
+def ba_sgd_solve_differentiable_f64(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor,
+                                    num_views: int, num_points: int, distortion: bool, *, learning_rate: float,
+                                    iterations: int, residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION,
+                                    want_errors: bool = False):
+    """The float64 fused gradient descent as an autograd node w.r.t. x0 and the (float64) observations: the
+    recording launch, and the adjoint kernel as its backward (``torch.ops.dava.ba_sgd_solve_differentiable_f64``).
+    Returns (x, errors | None); the errors carry no graph.  A float32 tensor raises ``TypeError``."""
+    N.require_device_tensor(x0, "parameters")
+    if x0.dtype != torch.float64 or observations.dtype != torch.float64:
+        raise TypeError(f"the float64 entry points take float64 tensors, got parameters {x0.dtype} and "
+                        f"observations {observations.dtype}")
+    obs = _c(observations.to(device=x0.device))  # (kept in the graph)
+    vis = _c(visibility.detach().to(device=x0.device, dtype=torch.uint8))
+    x, errs, _ = torch.ops.dava.ba_sgd_solve_differentiable_f64(
+        _c(x0), obs, vis, int(num_views), int(num_points), bool(distortion), float(learning_rate), int(iterations),
+        int(residual), bool(want_errors))
+    return x, (errs.detach() if want_errors else None)
+
+
 def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
                              residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> bool:
     """Host-only: does this shape have the float64 fused adjoint -- a recording forward

@@ -700,6 +700,63 @@ int dava_ba_sgd_backward_large(const DavaScene* scene, const DavaSgdConfig* conf
                                size_t tape_bytes, const float* x_out_grad, float* x0_grad, float* observations_grad,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- float64 fused gradient descent and its adjoint (additive to ABI 4) ----
+ * dava_ba_sgd_solve / _record / _backward on doubles: the same descent, x_{k+1} = x_k - learning_rate dE/dx(x_k)
+ * with the product rounded first and then the difference (no FMA), as torch does in float64; the same tape layout
+ * (B, K, Pv = round_up(P, 4)) in doubles; the same adjoint.  One entry point per operation, designed with the forms
+ * of the float64 kernels above from the start (no separate *_large_* twin):
+ *   descent  0  x, the gradient, the observations and the visibility in LDS (at M = 2 up to N = 1,962);
+ *            1  x and the gradient in LDS, the scene read in place (up to N = 3,353);
+ *            2  the scene in place, x and the gradient in a per-problem workspace slice of 2 Pv doubles (C5).
+ *   adjoint  0  the whole dual image and the accumulator of dL/dobs (2MN doubles) in LDS (up to N = 707);
+ *            1  the dual x and gradient in LDS, the scene in place, the step's dual dE/dobs in a workspace of
+ *               B * 4MN doubles (only with an observation gradient), the accumulator observations_grad itself,
+ *               zeroed and updated by the element's owner thread in form 0's arithmetic and order (up to
+ *               N = 1,667);
+ *            2  the dual x and gradient in a per-problem workspace slice of 4 Pv doubles too.
+ * Each operation takes the lowest form whose image fits 160 KiB; the F64_FORM override (1 | 2) raises it, never
+ * lowers it; DAVA_ERR_UNSUPPORTED (-DAVA_ERR_UNSUPPORTED from the form queries) where not even form 2's image fits.
+ * The adjoint's form is its own: it does not depend on the form the descent took.  Results are bitwise those of
+ * form 0 wherever more than one form runs.  No atomics: two launches give the same bits.
+ *
+ * Checks of the launches, in order and all before a device is touched: the scene; the config
+ * (DAVA_ERR_INVALID_ARGUMENT for NULL or negative iterations); an empty batch is DAVA_OK; NULL x0 / x_out (backward:
+ * NULL x_out_grad / x0_grad) is DAVA_ERR_INVALID_ARGUMENT; DAVA_ERR_UNSUPPORTED; a missing or short tape (K > 0) or
+ * workspace is DAVA_ERR_WORKSPACE.  Workspaces are uninitialised device memory: nothing is read before it is
+ * written.  A NULL workspace is accepted where the query says 0. */
+typedef struct DavaSgdConfigF64 {
+  double learning_rate;
+  int32_t iterations; /* K >= 0 */
+} DavaSgdConfigF64;
+
+/*   x0 (B, P), x_out (B, P) (may alias x0), error_trace_out (B, K) E(x_k) for k = 0 .. K-1, or NULL.
+ *   iterations == 0 is a device copy of x0 and no launch. */
+int dava_ba_sgd_solve_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config, const double* x0, double* x_out,
+                          double* error_trace_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The same launch (bitwise the same x_out and trace) that also writes x_k, k = 0 .. K-1, to the tape (pads zero). */
+int dava_ba_sgd_solve_record_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config, const double* x0,
+                                 double* x_out, double* error_trace_out, void* tape, size_t tape_bytes,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* Host-only: B * K * round_up(P, 4) * 8; 0 where the descent does not run the scene, and for K = 0. */
+size_t dava_ba_sgd_tape_bytes_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config);
+/* Host-only: 0, 1, 2 or minus the status. */
+int dava_ba_sgd_solve_form_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config);
+/* Host-only: exactly what the launch needs -- form 2: B * 2 Pv * 8 plus a 256-byte tail; forms 0 and 1: 0. */
+size_t dava_ba_sgd_solve_workspace_bytes_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config);
+
+/* dava_ba_sgd_backward's contract on doubles: x_out_grad (B, P) -> x0_grad (B, P) and observations_grad
+ * (B, M, N, 2), or NULL: then the dual dE/dobs is not formed and x0_grad is bitwise the same. */
+int dava_ba_sgd_backward_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config, const void* tape,
+                             size_t tape_bytes, const double* x_out_grad, double* x0_grad, double* observations_grad,
+                             void* workspace, size_t workspace_bytes, void* stream);
+/* Host-only: 0, 1, 2 or minus the status (the adjoint's own fit). */
+int dava_ba_sgd_backward_form_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config);
+/* Host-only; observations_grad != 0 when the observation gradient will be asked for.  Layout: [dual dE/dobs
+ * B * 4MN doubles, only in forms 1 and 2 with an observation gradient | form 2: B * 4 Pv doubles | a 256-byte tail];
+ * 0 where both blocks are empty (form 0; form 1 without an observation gradient). */
+size_t dava_ba_sgd_backward_workspace_bytes_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config,
+                                                int observations_grad);
+
 /* ---- test and A/B hooks ----
  * The library makes its launch choices itself (LDS or global-vector mode, waves per workgroup,
  * on-chip history entries, work queue, ...) and reads NOTHING from the environment.  Tests and A/B

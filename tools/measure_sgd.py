@@ -19,8 +19,17 @@ only forms 1 and 2 of the adjoint run -- C5 (16 x 4096, B = 256: form 2) and a t
 gradients); and at C3 (B = 8192) the adjoint in form 0 and raised to forms 1 and 2 through the F32_DUAL_FORM
 override, alternated run by run.  Lines are appended to profiles/sgd_large.jsonl.
 
+--mode f64: the float64 fused descent (dava_ba_sgd_solve_f64) against K x dava_ba_evaluate_f64 with torch updates,
+and the float64 descent + gradient (the recording launch and the adjoint kernel, SGDSolver on a float64_descent=True
+objective) against the torch loop with create_graph on a float64_derivatives=True objective (its double backward is
+one dava_ba_second_order_f64 launch per step) -- the paths a float64 SGDSolver call took before the fused ones.
+C2 (B = 1024) and C3 (B = 8192) at lr = 1e-4, C5 (B = 256) at lr = 1e-5, K = 100; the method of the default mode
+(interleaved in one process, both orders, best of >= 5 rounds after a warm-up, HIP events), every round's times
+kept.  Lines are written to profiles/sgd_f64.jsonl.
+
 usage: python tools/measure_sgd.py [--out FILE] [--repeats 5] [--configs c2:1024,c3:8192] [--iterations 100]
        python tools/measure_sgd.py --mode large [--out FILE] [--repeats 5] [--iterations 100]
+       python tools/measure_sgd.py --mode f64 [--out FILE] [--repeats 5] [--configs c2:1024,c3:8192,c5:256]
 """
 import argparse
 import json
@@ -163,6 +172,88 @@ def measure_large(shape, b, k, lr, repeats, forms, dev):
     return rec
 
 
+def measure_f64(shape, b, k, lr, repeats, dev):
+    from deep_attention_visual_odometry_amd import ReprojectionError, SGDSolver, make_scenes, native_ops
+
+    m, n, dist = SHAPES[shape]
+    s = make_scenes(b, m, n, distortion=dist, seed=7, drop=0.0 if dist else 0.1)
+    x0 = torch.tensor(s.initial, device=dev).double()
+    obs = torch.tensor(s.observations, device=dev).double()
+    vis = torch.tensor(s.visibility, device=dev).to(torch.uint8)
+    w = torch.randn(x0.shape, generator=torch.Generator().manual_seed(3), dtype=torch.float64).to(dev)
+    solver = SGDSolver(lr, k)
+    forms = (native_ops.sgd_solve_form_f64(b, m, n, dist, k), native_ops.sgd_backward_form_f64(b, m, n, dist, k))
+    large = native_ops.second_order_form_f64(b, m, n, dist) != 0  # the loop's double backward beyond the LDS image
+
+    def fused_forward():
+        return native_ops.ba_sgd_solve_f64(x0, obs, vis, m, n, dist, learning_rate=lr, iterations=k)[0]
+
+    def composed_forward():
+        x = x0
+        for _ in range(k):
+            _, g, _ = native_ops.ba_evaluate(x, obs, vis, m, n, dist, want_grad=True)
+            x = x - lr * g
+        return x
+
+    def gradient(loop):
+        xg, og = x0.clone().requires_grad_(True), obs.clone().requires_grad_(True)
+        if loop:
+            fn = ReprojectionError(og, vis, m, n, dist, float64_derivatives=True, float64_large_gradients=large)
+            out = solver._loop(xg, fn)
+        else:
+            out = solver(xg, ReprojectionError(og, vis, m, n, dist, float64_descent=True))
+        gx, go = torch.autograd.grad((out * w).sum(), [xg, og])
+        return out.detach(), gx, go
+
+    paths = {"fused_forward": fused_forward, "composed_forward": composed_forward,
+             "fused_gradient": lambda: gradient(False), "composed_gradient": lambda: gradient(True)}
+    rounds = {name: [] for name in paths}
+    outs = {}
+    for pair in (("fused_forward", "composed_forward"), ("fused_gradient", "composed_gradient")):
+        for name in pair:  # warm-up: code objects, allocator
+            outs[name] = timed(paths[name], dev)[1]
+        for rep in range(repeats):
+            for name in (pair if rep % 2 == 0 else pair[::-1]):  # both orders
+                rounds[name].append(timed(paths[name], dev)[0])
+    finite = torch.isfinite(outs["fused_forward"]).all(dim=-1) & torch.isfinite(outs["composed_forward"]).all(dim=-1)
+
+    def rel(a, c):
+        r = ((a - c).norm(dim=-1) / c.norm(dim=-1))[finite]
+        r = r[torch.isfinite(r)]
+        return {"max": float(r.max()), "median": float(r.median())}
+
+    rec = {"mode": "f64", "shape": shape, "B": b, "K": k, "learning_rate": lr, "P": x0.shape[1], "repeats": repeats,
+           "descent_form": forms[0], "adjoint_form": forms[1], "rows_compared": int(finite.sum())}
+    for name, ms in rounds.items():
+        rec[name + "_ms"] = round(min(ms), 3)
+        rec[name + "_rounds_ms"] = [round(t, 3) for t in ms]
+        rec[name + "_problems_per_s"] = round(b / (min(ms) * 1e-3), 1)
+    for what in ("forward", "gradient"):
+        fused, composed = rounds["fused_" + what], rounds["composed_" + what]
+        rec[what + "_speedup"] = round(min(composed) / min(fused), 2)
+        rec[what + "_fused_faster_every_round"] = all(f < c for f, c in zip(fused, composed))
+    rec["forward_max_rel_diff"] = rel(outs["fused_forward"], outs["composed_forward"])
+    rec["gradient_x0_max_rel_diff"] = rel(outs["fused_gradient"][1] - w, outs["composed_gradient"][1] - w)
+    rec["gradient_obs_max_rel_diff"] = rel(outs["fused_gradient"][2].flatten(1),
+                                           outs["composed_gradient"][2].flatten(1))
+    return rec
+
+
+def main_f64(args, dev):
+    out = args.out or os.path.join(REPO, "profiles", "sgd_f64.jsonl")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    configs = "c2:1024,c3:8192,c5:256" if args.configs == "c2:1024,c3:8192" else args.configs
+    lines = []
+    for config in configs.split(","):
+        shape, b = config.split(":")
+        lr = args.learning_rate if args.learning_rate is not None else (1e-5 if shape == "c5" else 1e-4)
+        rec = measure_f64(shape, int(b), args.iterations, lr, max(args.repeats, 5), dev)
+        print(json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+        with open(out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def main_large(args, dev):
     out = args.out or os.path.join(REPO, "profiles", "sgd_large.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
@@ -176,7 +267,7 @@ def main_large(args, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("solve", "large"), default="solve")
+    ap.add_argument("--mode", choices=("solve", "large", "f64"), default="solve")
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--configs", default="c2:1024,c3:8192")
@@ -188,6 +279,8 @@ def main():
     dev = torch.device("cuda", 0)
     if args.mode == "large":
         return main_large(args, dev)
+    if args.mode == "f64":
+        return main_f64(args, dev)
     args.out = args.out or os.path.join(REPO, "profiles", "sgd_solve.jsonl")
     args.learning_rate = 1e-4 if args.learning_rate is None else args.learning_rate
     lines = []
