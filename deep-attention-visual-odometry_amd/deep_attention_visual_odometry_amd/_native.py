@@ -28,6 +28,8 @@ LIB_PATH = (_DEBUG_ENV and os.environ.get("DAVA_LIB")) or os.path.join(_HERE, "_
 LIBRARY_KNOBS = ("FORCE_GV", "GV_NO_XL", "SOLVE_WAVES", "WG_PER_CU", "LDS_HISTORY", "STAGGER", "STAGGER_LEVELS",
                  "NO_PPT", "NO_QUEUE", "ADJ_GV_WAVES", "ADJ_FORCE_GV", "ADJ_LDS_ENTRIES", "ADJ_GD_HBM",
                  "COMPACT_SWITCH", "GV_SCALAR_SLICE", "ADJ_SC_GLOBAL", "F64_FORM", "F32_DUAL_FORM")
+# knobs appended to the library's list later on (kept apart: the tuple above is pinned, last entry included)
+LIBRARY_KNOBS_APPENDED = ("L1_SOLVE_FORM",)
 # GENERIC_BACKWARD: differentiate a fused objective's solve with the generic loop, not the adjoint;
 # GENERIC_TRAINING: training mode's drop path with the generic loop and torch's own RNG;
 # GENERIC_DENSE: the generic loop keeps the reference's dense (B, P, P) inverse Hessian even without a graph
@@ -120,6 +122,25 @@ class DavaSgdConfigF64(ctypes.Structure):
     _fields_ = [
         ("learning_rate", ctypes.c_double),
         ("iterations", _c_i32),
+    ]
+
+
+class DavaL1SolveConfig(ctypes.Structure):
+    """The fused legacy solve (`dava_l1_camera_solve_*`): the float fields are the values the Python modules hold
+    as float32 tensors; the step distances are Python floats there, so they cross as doubles."""
+    _fields_ = [
+        ("max_iterations", _c_i32),
+        ("widen_iterations", _c_i32),
+        ("zoom_iterations", _c_i32),
+        ("constrain", _c_i32),
+        ("max_step_distance", ctypes.c_double),
+        ("min_step_distance", ctypes.c_double),
+        ("derived_inverse_pixel_ratio", ctypes.c_double),
+        ("epsilon", ctypes.c_float),
+        ("max_step_size", ctypes.c_float),
+        ("sufficient_decrease", ctypes.c_float),
+        ("curvature", ctypes.c_float),
+        ("slope_scale", ctypes.c_float),
     ]
 
 
@@ -251,6 +272,13 @@ for _t in ("f32", "f64"):
                                           + [_scalar] * 4 + [_vp, _vp, _vp]),
         f"dava_l1_camera_vjp_{_t}": (ctypes.c_int, [_c_i64, _c_i32, _c_i32, _c_i32] + [_vp] * 8 + [_scalar] * 4
                                      + [_vp, _vp, _c_i32, _vp, _vp]),
+        # the fused legacy solve (csrc/camera_l1_solve.hip): the evaluate entry's scene and model arguments, the
+        # config, 6 parameter outputs, error, iterations, 3 traces, workspace, bytes, stream
+        f"dava_l1_camera_solve_{_t}": (ctypes.c_int, [_c_i64, _c_i32, _c_i32, _c_i32] + [_vp] * 8 + [_scalar] * 4
+                                       + [ctypes.POINTER(DavaL1SolveConfig)] + [_vp] * 11
+                                       + [_vp, ctypes.c_size_t, _vp]),
+        f"dava_l1_camera_solve_form_{_t}": (ctypes.c_int, [_c_i32, _c_i32]),
+        f"dava_l1_camera_solve_workspace_bytes_{_t}": (ctypes.c_size_t, [_c_i64, _c_i32, _c_i32, _c_i32]),
         f"dava_bfgs_initial_scale_backward_{_t}": (ctypes.c_int, [_c_i64, _c_i64] + [_vp] * 6),
         f"dava_bfgs_scale_matrix_backward_{_t}": (ctypes.c_int, [_c_i64, _c_i64] + [_vp] * 6),
         f"dava_bfgs_search_direction_backward_{_t}": (ctypes.c_int, [_c_i64, _c_i64] + [_vp] * 6),
@@ -304,7 +332,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             raise NativeLibraryError("libdava_ba.so ABI version mismatch")
         _lib = lib
         if _DEBUG_ENV:  # A/B runs: the DAVA_<NAME> variables, read once, here
-            for k in LIBRARY_KNOBS + PYTHON_KNOBS:
+            for k in LIBRARY_KNOBS + LIBRARY_KNOBS_APPENDED + PYTHON_KNOBS:
                 v = os.environ.get("DAVA_" + k)
                 if v is None:
                     continue
@@ -337,7 +365,7 @@ def set_debug_override(name: str, value: int) -> None:
     if name in PYTHON_KNOBS:
         _py_knobs[name] = int(value) if value >= 0 else -1
         return
-    if name not in LIBRARY_KNOBS:
+    if name not in LIBRARY_KNOBS + LIBRARY_KNOBS_APPENDED:
         raise ValueError(f"unknown override {name!r}")
     lib = load_library()
     if hasattr(lib, "dava_debug_set_override"):

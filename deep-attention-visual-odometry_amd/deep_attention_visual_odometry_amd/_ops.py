@@ -1375,6 +1375,84 @@ def _(focal, cx, cy, translation, lie, world, target, visibility, minimum_z_dist
     return focal.new_empty((b, e, 3 + 6 * m + 3 * (n - 2)))
 
 
+# ------------------------------------------------ the legacy solver fused (BFGSCameraSolver + its line search)
+
+def l1_solve_config(max_iterations: int, widen_iterations: int, zoom_iterations: int, constrain: bool,
+                    epsilon: float, max_step_distance: float, min_step_distance: float, max_step_size: float,
+                    sufficient_decrease: float, curvature: float, slope_scale: float,
+                    derived_pixel_ratio: float) -> N.DavaL1SolveConfig:
+    return N.DavaL1SolveConfig(int(max_iterations), int(widen_iterations), int(zoom_iterations), int(bool(constrain)),
+                               float(max_step_distance), float(min_step_distance), float(derived_pixel_ratio),
+                               float(epsilon), float(max_step_size), float(sufficient_decrease), float(curvature),
+                               float(slope_scale))
+
+
+@torch.library.custom_op("dava::l1_camera_solve", mutates_args=(), device_types=_CUDA)
+def l1_camera_solve(focal: Tensor, cx: Tensor, cy: Tensor, translation: Tensor, lie: Tensor, world: Tensor,
+                    target: Tensor, visibility: Tensor, minimum_z_distance: float, maximum_pixel_ratio: float,
+                    max_gradient: float, error_scale: float, max_iterations: int, widen_iterations: int,
+                    zoom_iterations: int, constrain: bool, epsilon: float, max_step_distance: float,
+                    min_step_distance: float, max_step_size: float, sufficient_decrease: float, curvature: float,
+                    slope_scale: float, derived_pixel_ratio: float, want_traces: bool
+                    ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``dava_l1_camera_solve``: ``BFGSCameraSolver.forward`` with ``LineSearchStrongWolfeConditions`` inside it, over
+    a ``PinholeCameraModelL1``, in one launch (csrc/camera_l1_solve.hip).  Input shapes as ``l1_camera_evaluate``.
+    Returns (focal, cx, cy, translation, lie, world) at the solved point, its error (B, E), the iterations each
+    estimate was updated in (B, E) int32, and -- or empty -- the traces (B, E, max_iterations): error, alpha, exit
+    (int32).  The inverse Hessian's workspace, where the form needs one, comes from torch's allocator.  Not
+    differentiable."""
+    b, e = focal.shape
+    m, n = target.shape[1], target.shape[2]
+    for t, shape, what in ((cx, (b, e), "cx"), (cy, (b, e), "cy"), (translation, (b, e, m, 3), "translation"),
+                           (lie, (b, e, m, 3), "orientation"), (world, (b, e, n - 2, 3), "world_points"),
+                           (target, (b, m, n, 2), "true_projected_points")):
+        _same(t, focal, shape, what)
+    if tuple(visibility.shape) != (b, m, n) or visibility.dtype != torch.uint8 or not visibility.is_contiguous():
+        raise ValueError("visibility must be a contiguous (B, M, N) uint8 tensor")
+    if max_iterations < 1 or widen_iterations < 0 or zoom_iterations < 0:
+        raise ValueError("the fused legacy solve needs max_iterations >= 1 and non-negative trial counts")
+    if n < 4:
+        raise ValueError("the fused legacy solve needs at least 4 points (add() has no z block at 3)")
+    lib = N.load_library()
+    dt = _dt(focal)
+    if getattr(lib, f"dava_l1_camera_solve_form_{dt}")(m, n) < 0:
+        raise ValueError("this scene has no fused legacy solve: its evaluation scratch and solver state do not fit "
+                         "one workgroup's LDS")
+    cfg = l1_solve_config(max_iterations, widen_iterations, zoom_iterations, constrain, epsilon, max_step_distance,
+                          min_step_distance, max_step_size, sufficient_decrease, curvature, slope_scale,
+                          derived_pixel_ratio)
+    need = int(getattr(lib, f"dava_l1_camera_solve_workspace_bytes_{dt}")(b, e, m, n))
+    ws = _scratch(need, focal.device) if need else None
+    outs = [torch.empty_like(t) for t in (focal, cx, cy, translation, lie, world)]
+    err = focal.new_empty((b, e))
+    iters = focal.new_empty((b, e), dtype=torch.int32)
+    k = max_iterations
+    tr_err = focal.new_empty((b, e, k)) if want_traces else _empty0(focal)
+    tr_alpha = focal.new_empty((b, e, k)) if want_traces else _empty0(focal)
+    tr_exit = focal.new_empty((b, e, k), dtype=torch.int32) if want_traces else _empty0(focal, torch.int32)
+    with torch.cuda.device(focal.device):
+        N.check(getattr(lib, f"dava_l1_camera_solve_{dt}")(
+            b, e, m, n, N.ptr(focal), N.ptr(cx), N.ptr(cy), N.ptr(translation), N.ptr(lie), N.ptr(world),
+            N.ptr(target), N.ptr(visibility), minimum_z_distance, maximum_pixel_ratio, max_gradient, error_scale,
+            cfg, *[N.ptr(t) for t in outs], N.ptr(err), N.ptr(iters),
+            *[N.ptr(t) if want_traces else None for t in (tr_err, tr_alpha, tr_exit)],
+            N.ptr(ws) if need else None, ws.numel() if need else 0, N.stream_of(focal.device)),
+            "dava_l1_camera_solve")
+    return (*outs, err, iters, tr_err, tr_alpha, tr_exit)
+
+
+@l1_camera_solve.register_fake
+def _(focal, cx, cy, translation, lie, world, target, visibility, minimum_z_distance, maximum_pixel_ratio,
+      max_gradient, error_scale, max_iterations, widen_iterations, zoom_iterations, constrain, epsilon,
+      max_step_distance, min_step_distance, max_step_size, sufficient_decrease, curvature, slope_scale,
+      derived_pixel_ratio, want_traces):
+    b, e = focal.shape
+    tr = (b, e, max_iterations) if want_traces else (0,)
+    return (*[torch.empty_like(t) for t in (focal, cx, cy, translation, lie, world)], focal.new_empty((b, e)),
+            focal.new_empty((b, e), dtype=torch.int32), focal.new_empty(tr), focal.new_empty(tr),
+            focal.new_empty(tr, dtype=torch.int32))
+
+
 # ---------------------------------------- float64 fused gradient descent (SGDSolver) and its adjoint
 # One operator per operation: the C symbols take forms 0, 1 and 2 themselves (csrc/sgd_solve_f64.hip,
 # sgd_adjoint_f64.hip), with a workspace from torch's allocator sized by the library's host queries.
@@ -1528,4 +1606,4 @@ OPS = ("bfgs_solve", "ba_solve", "ba_solve_record", "ba_solve_backward", "ba_eva
        "wolfe_init", "wolfe_propose", "wolfe_update", "l1_camera_evaluate", "l1_camera_vjp",
        "ba_sgd_solve", "ba_sgd_solve_differentiable", "ba_sgd_backward", "ba_second_order_large",
        "ba_sgd_solve_differentiable_large", "ba_sgd_backward_large", "ba_sgd_solve_f64",
-       "ba_sgd_solve_differentiable_f64", "ba_sgd_backward_f64")
+       "ba_sgd_solve_differentiable_f64", "ba_sgd_backward_f64", "l1_camera_solve")

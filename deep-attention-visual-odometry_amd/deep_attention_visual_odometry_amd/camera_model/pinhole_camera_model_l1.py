@@ -79,6 +79,9 @@ class PinholeCameraModelL1(IOptimisableFunction):
     CY = 1
     F = 2
     VIEW_START = 3
+    # the constructor's default; add() and masked_update() build their models without the argument, so every model
+    # they make has it whatever the original's was (the fused legacy solve reproduces that)
+    DEFAULT_MAXIMUM_PIXEL_RATIO = 5.0
 
     def __init__(
         self,
@@ -91,7 +94,7 @@ class PinholeCameraModelL1(IOptimisableFunction):
         true_projected_points: torch.Tensor,
         visibility_mask: torch.Tensor,
         minimum_z_distance: float = 1e-3,
-        maximum_pixel_ratio: float = 5.0,
+        maximum_pixel_ratio: float = DEFAULT_MAXIMUM_PIXEL_RATIO,
         constrain: bool = False,
         max_gradient: float = -1.0,
         enable_error_gradients: bool = True,

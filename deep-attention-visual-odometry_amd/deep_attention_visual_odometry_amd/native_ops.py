@@ -796,3 +796,49 @@ class WolfeState:
 
     def update(self, trial: int, c1: float, c2: float, strong: bool) -> None:
         torch.ops.dava.wolfe_update(self.state, self.flags, int(trial), float(c1), float(c2), bool(strong))
+
+
+# ---- the legacy solver fused (csrc/camera_l1_solve.hip) ----
+
+def l1_solve_form(num_views: int, num_points: int, dtype: torch.dtype = torch.float64) -> int:
+    """``dava_l1_camera_solve_form_*`` (host-only): 0 the inverse Hessian in LDS, 1 in the workspace, -1 where the
+    fused legacy solve does not run this shape."""
+    suffix = "f32" if dtype == torch.float32 else "f64"
+    return int(getattr(N.load_library(), f"dava_l1_camera_solve_form_{suffix}")(int(num_views), int(num_points)))
+
+
+def l1_solve_workspace_bytes(batch: int, estimates: int, num_views: int, num_points: int,
+                             dtype: torch.dtype = torch.float64) -> int:
+    """``dava_l1_camera_solve_workspace_bytes_*`` (host-only): form 1's B E P^2 elements, else 0."""
+    suffix = "f32" if dtype == torch.float32 else "f64"
+    return int(getattr(N.load_library(), f"dava_l1_camera_solve_workspace_bytes_{suffix}")(
+        int(batch), int(estimates), int(num_views), int(num_points)))
+
+
+def l1_camera_solve(focal: torch.Tensor, cx: torch.Tensor, cy: torch.Tensor, translation: torch.Tensor,
+                    lie: torch.Tensor, world: torch.Tensor, target: torch.Tensor, visibility: torch.Tensor, *,
+                    minimum_z_distance: float, inverse_pixel_ratio: float, max_gradient: float, error_scale: float,
+                    max_iterations: int, widen_iterations: int, zoom_iterations: int, constrain: bool, epsilon: float,
+                    max_step_distance: float, min_step_distance: float, max_step_size: float,
+                    sufficient_decrease: float, curvature: float, slope_scale: float, derived_pixel_ratio: float,
+                    want_traces: bool = True):
+    """The whole ``BFGSCameraSolver.forward`` in one launch (``torch.ops.dava.l1_camera_solve``).  Tensors: focal,
+    cx, cy (B, E); translation, lie (B, E, M, 3); world (B, E, N-2, 3); target (B, M, N, 2); visibility (B, M, N),
+    all on one ROCm device, the floating ones of one dtype (float32 or float64).  Returns a dict: the six solved
+    tensors under their argument names, ``error`` (B, E), ``iterations`` (B, E) int32 and, with ``want_traces``,
+    ``trace_error`` / ``trace_alpha`` / ``trace_exit`` (B, E, max_iterations), else None."""
+    ts = [_float_on_device(t, what) for t, what in ((focal, "focal_length"), (cx, "cx"), (cy, "cy"),
+                                                    (translation, "translation"), (lie, "orientation"),
+                                                    (world, "world_points"), (target, "true_projected_points"))]
+    vis = _c(visibility.detach().to(device=ts[0].device, dtype=torch.uint8))
+    out = torch.ops.dava.l1_camera_solve(
+        *ts, vis, float(minimum_z_distance), float(inverse_pixel_ratio), float(max_gradient), float(error_scale),
+        int(max_iterations), int(widen_iterations), int(zoom_iterations), bool(constrain), float(epsilon),
+        float(max_step_distance), float(min_step_distance), float(max_step_size), float(sufficient_decrease),
+        float(curvature), float(slope_scale), float(derived_pixel_ratio), bool(want_traces))
+    names = ("focal", "cx", "cy", "translation", "lie", "world", "error", "iterations", "trace_error", "trace_alpha",
+             "trace_exit")
+    res = dict(zip(names, out))
+    if not want_traces:
+        res.update(trace_error=None, trace_alpha=None, trace_exit=None)
+    return res

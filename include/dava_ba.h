@@ -757,12 +757,83 @@ int dava_ba_sgd_backward_form_f64(const DavaSceneF64* scene, const DavaSgdConfig
 size_t dava_ba_sgd_backward_workspace_bytes_f64(const DavaSceneF64* scene, const DavaSgdConfigF64* config,
                                                 int observations_grad);
 
+/* ---- the legacy solver fused: BFGSCameraSolver + LineSearchStrongWolfeConditions in one launch (additive to ABI 4) ----
+ * Replaces BFGSCameraSolver.forward(function) (solvers/bfgs_camera_solver.py, with
+ * solvers/line_search_strong_wolfe_conditions.py inside it) over a PinholeCameraModelL1: one workgroup per
+ * (batch item, estimate) runs max_iterations of [gradient; d = -g, then -H g; the max/min step clamp; the widening
+ * phase; the secant zoom; H0 = (s.y / max(y.y, 1e-5)) I on the first iteration; the rank-2 update; masked_update;
+ * updating &= error > epsilon], every evaluation being the model of dava_l1_camera_evaluate.  An estimate whose
+ * error is no longer above epsilon is frozen: its workgroup stops there.  No gradients flow through this entry.
+ *
+ * Scene and model arguments are dava_l1_camera_evaluate's (inverse_pixel_ratio is the INPUT model's; points >= 4:
+ * the model's add() has no z block at 3 points).  The config:
+ *   max_iterations, widen_iterations (the line search's ceil(log2(max_step_size))), zoom_iterations, constrain
+ *   (add()'s clamps: focal to [inverse pixel ratio, 1e3], cx and cy to [-1, 1], each lie vector re-wrapped to
+ *   [-pi, pi));
+ *   epsilon, max_step_size, sufficient_decrease, curvature, slope_scale (the line search's sqrt(float32(1 / P))):
+ *   float32 values, because the Python modules hold them as float32 tensors; float64 data widens them;
+ *   max_step_distance, min_step_distance: doubles, because the Python modules hold them as Python floats (float64
+ *   data compares and divides by the unrounded values; float32 data rounds them);
+ *   derived_inverse_pixel_ratio: the ratio of every model add() / masked_update() makes (they do not pass
+ *   maximum_pixel_ratio on, so it is the constructor default's 1/5 whatever the input model's is).
+ * Outputs: the six parameter tensors in the inputs' shapes, error_out (batch, estimates): that point's error,
+ * iterations_out (batch, estimates): the iterations during which the estimate was still updating.  Optional
+ * traces, each (batch, estimates, max_iterations) or NULL: trace_error (the error after each iteration's
+ * masked_update), trace_alpha (the returned step's alpha; the step is alpha d), trace_exit (0 estimate already
+ * frozen, 1 accepted while widening, 2 accepted in zoom, 3 unfinished from widening, 4 unfinished from zoom).
+ *
+ * Two forms by what fits 150 KiB of one workgroup's LDS beside the evaluation's (views, points, 4) scratch and the
+ * O(P) state: 0 the P x P inverse Hessian in LDS, 1 in a per-estimate slice of the workspace (batch estimates P^2
+ * elements, uninitialised); dava_l1_camera_solve_form_* returns the form or -1 where even form 1 does not fit.  The
+ * L1_SOLVE_FORM override (1) raises the form, never lowers it; results are bitwise the same in both forms.
+ * Deterministic.  Checked on the host before any device call, in order: sizes (negative counts, views < 1,
+ * points < 4, NULL config: DAVA_ERR_INVALID_ARGUMENT); an empty batch or max_iterations == 0 is DAVA_OK (nothing is
+ * written); a NULL scene, model, parameter output, error_out or iterations_out pointer is
+ * DAVA_ERR_INVALID_ARGUMENT; DAVA_ERR_UNSUPPORTED; a missing or short workspace is DAVA_ERR_WORKSPACE. */
+typedef struct DavaL1SolveConfig {
+  int32_t max_iterations;
+  int32_t widen_iterations;
+  int32_t zoom_iterations;
+  int32_t constrain;
+  double max_step_distance;
+  double min_step_distance;
+  double derived_inverse_pixel_ratio;
+  float epsilon;
+  float max_step_size;
+  float sufficient_decrease;
+  float curvature;
+  float slope_scale;
+} DavaL1SolveConfig;
+
+int dava_l1_camera_solve_f32(int64_t batch, int32_t estimates, int32_t views, int32_t points, const float* focal,
+                             const float* cx, const float* cy, const float* translation, const float* lie_vector,
+                             const float* world_points, const float* true_points, const uint8_t* visibility,
+                             float minimum_z_distance, float inverse_pixel_ratio, float max_gradient,
+                             float error_scale, const DavaL1SolveConfig* config, float* focal_out, float* cx_out,
+                             float* cy_out, float* translation_out, float* lie_vector_out, float* world_points_out,
+                             float* error_out, int32_t* iterations_out, float* trace_error, float* trace_alpha,
+                             int32_t* trace_exit, void* workspace, size_t workspace_bytes, void* stream);
+int dava_l1_camera_solve_f64(int64_t batch, int32_t estimates, int32_t views, int32_t points, const double* focal,
+                             const double* cx, const double* cy, const double* translation, const double* lie_vector,
+                             const double* world_points, const double* true_points, const uint8_t* visibility,
+                             double minimum_z_distance, double inverse_pixel_ratio, double max_gradient,
+                             double error_scale, const DavaL1SolveConfig* config, double* focal_out, double* cx_out,
+                             double* cy_out, double* translation_out, double* lie_vector_out,
+                             double* world_points_out, double* error_out, int32_t* iterations_out,
+                             double* trace_error, double* trace_alpha, int32_t* trace_exit, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* Host-only. */
+int dava_l1_camera_solve_form_f32(int32_t views, int32_t points);
+int dava_l1_camera_solve_form_f64(int32_t views, int32_t points);
+size_t dava_l1_camera_solve_workspace_bytes_f32(int64_t batch, int32_t estimates, int32_t views, int32_t points);
+size_t dava_l1_camera_solve_workspace_bytes_f64(int64_t batch, int32_t estimates, int32_t views, int32_t points);
+
 /* ---- test and A/B hooks ----
  * The library makes its launch choices itself (LDS or global-vector mode, waves per workgroup,
  * on-chip history entries, work queue, ...) and reads NOTHING from the environment.  Tests and A/B
  * measurements override a choice by name (FORCE_GV, GV_NO_XL, SOLVE_WAVES, WG_PER_CU, LDS_HISTORY,
  * STAGGER, STAGGER_LEVELS, NO_PPT, NO_QUEUE, ADJ_GV_WAVES, ADJ_FORCE_GV, ADJ_LDS_ENTRIES, ADJ_GD_HBM,
- * COMPACT_SWITCH, GV_SCALAR_SLICE, ADJ_SC_GLOBAL, F64_FORM, F32_DUAL_FORM; csrc/dava_debug.hpp); value < 0 restores the
+ * COMPACT_SWITCH, GV_SCALAR_SLICE, ADJ_SC_GLOBAL, F64_FORM, F32_DUAL_FORM, L1_SOLVE_FORM; csrc/dava_debug.hpp); value < 0 restores the
  * library's choice.  Process-wide, not thread-safe, host-only.  DAVA_ERR_INVALID_ARGUMENT for an
  * unknown name.                                                                                   */
 int dava_debug_set_override(const char* name, int64_t value);
