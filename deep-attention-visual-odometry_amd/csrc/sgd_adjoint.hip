@@ -102,126 +102,66 @@ __global__ __launch_bounds__(kBlock) void sgd_ba_adjoint_kernel(sgd_adjoint_args
   }
 }
 
-// DAVA_OK where the adjoint runs this scene / config: the config's validity and the fit of the adjoint's own
-// image, whatever form (or override) the forward takes.  check_scene(scene, ...) must have passed.
-static int sgd_adjoint_status(const DavaScene* scene, const DavaSgdConfig* config, int* lds_out) {
-  if (!config || config->iterations < 0) return DAVA_ERR_INVALID_ARGUMENT;
-  if (!sgd_sizes_sane(scene)) return DAVA_ERR_UNSUPPORTED;
-  const int lds = plan_second(scene).lds_bytes + sgd_adjoint_acc_bytes(scene->num_views, scene->num_points);
-  if (lds > kMaxLds) return DAVA_ERR_UNSUPPORTED;
-  if (lds_out) *lds_out = lds;
-  return DAVA_OK;
-}
-
-// The adjoint for a scene of any size (dava_ba_sgd_backward_large and its queries): the form, its LDS image and
-// its workspace [dual dE/dobs of one step B x 4MN floats, only with an observation gradient | form 2: B x 4 Pv
-// floats | 256-byte tail].  check_scene(scene, ...) must have passed.
-struct SgdAdjointLarge {
-  int status, form, lds;
-  size_t obsd_bytes, vector_bytes;
+// ---- host side: one plan and one launcher for the entry points (as ba_second_order.hip) ----
+struct SgdAdjointLaunch {
+  int status;
+  bool launch;  // false: return `status` (a refusal, or DAVA_OK for an empty batch)
+  int form, lds;
+  size_t tape_bytes;
+  size_t obsd_bytes;    // workspace, forms 1 and 2 with an observation gradient: a step's dual dE/dobs, B x 4MN floats
+  size_t vector_bytes;  // workspace after it, form 2: the dual x and g, B x 4 Pv floats
+  LargeSgdAdjointArgs args;  // the form-0 kernel takes its base
   size_t workspace_bytes() const { return obsd_bytes + vector_bytes + kSecondTailBytes; }
 };
-static SgdAdjointLarge sgd_adjoint_large(const DavaScene* scene, const DavaSgdConfig* config, bool obs_grad) {
-  SgdAdjointLarge p{};
+
+// What a scene / config needs, from its shape alone, whatever form (or override) the forward takes: the queries and
+// the launch's checks read the same numbers.  any_form false: the symbols of the LDS image, form 0 by fit alone.
+// check_scene(sc, ...) must have passed.
+static SgdAdjointLaunch sgd_adjoint_shape(const DavaScene* sc, const DavaSgdConfig* config, bool obs_grad,
+                                          bool any_form) {
+  SgdAdjointLaunch p{};
   p.form = -1;
   p.status = DAVA_ERR_INVALID_ARGUMENT;
   if (!config || config->iterations < 0) return p;
   p.status = DAVA_ERR_UNSUPPORTED;
-  const int M = scene->num_views, N = scene->num_points, Pv = round_up(scene->num_parameters, 4);
-  p.form = choose_second_form(scene, sgd_adjoint_acc_bytes(M, N));
+  const int M = sc->num_views, N = sc->num_points, Pv = round_up(sc->num_parameters, 4);
+  const int acc = sgd_adjoint_acc_bytes(M, N);
+  if (any_form) p.form = choose_second_form(sc, acc);
+  else if (sgd_sizes_sane(sc) && plan_second(sc).lds_bytes + acc <= kMaxLds) p.form = 0;
   if (p.form < 0) return p;
   p.status = DAVA_OK;
-  p.lds = p.form == 0 ? plan_second(scene).lds_bytes + sgd_adjoint_acc_bytes(M, N)
-                      : carve_second_large(M, Pv, p.form).total_bytes;
-  p.obsd_bytes = p.form != 0 && obs_grad ? (size_t)scene->batch * 4 * M * N * sizeof(float) : 0;
-  p.vector_bytes = p.form == 2 ? (size_t)scene->batch * 4 * Pv * sizeof(float) : 0;
+  p.lds = p.form == 0 ? plan_second(sc).lds_bytes + acc : carve_second_large(M, Pv, p.form).total_bytes;
+  p.tape_bytes = sgd_tape_bytes(sc->batch, config->iterations, Pv);
+  p.obsd_bytes = p.form != 0 && obs_grad ? (size_t)sc->batch * 4 * M * N * sizeof(float) : 0;
+  p.vector_bytes = p.form == 2 ? (size_t)sc->batch * 4 * Pv * sizeof(float) : 0;
   return p;
 }
 
-template <int FORM>
-static int launch_sgd_adjoint(const LargeSgdAdjointArgs& args, const DavaScene* scene, int lds, void* stream) {
-  const sgd_adjoint_args_t<FORM>& a = args;
-  with_flag(scene->residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
-    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
-    launch_lds(sgd_ba_adjoint_kernel<kRes, FORM>, scene->batch, kBlock, lds, static_cast<hipStream_t>(stream), a);
-  });
-  return launched();
-}
-
-}  // namespace dava
-
-using namespace dava;
-
-extern "C" int dava_ba_sgd_backward_supported(const DavaScene* scene, const DavaSgdConfig* config) {
-  if (check_scene(scene, false) != DAVA_OK) return 0;
-  return sgd_adjoint_status(scene, config, nullptr) == DAVA_OK ? 1 : 0;
-}
-
-extern "C" int dava_ba_sgd_backward(const DavaScene* scene, const DavaSgdConfig* config, const void* tape,
-                                    size_t tape_bytes, const float* x_out_grad, float* x0_grad,
-                                    float* observations_grad, void* stream) {
+// the checks of the entry points, in their order
+static SgdAdjointLaunch plan_sgd_adjoint(const DavaScene* scene, const DavaSgdConfig* config, const void* tape,
+                                         size_t tape_bytes, const float* x_out_grad, float* x0_grad,
+                                         float* observations_grad, void* workspace, size_t workspace_bytes,
+                                         bool any_form) {
+  SgdAdjointLaunch p{};
+  const auto refuse = [&p](int st) {
+    p.status = st;
+    return p;
+  };
   const int st = check_scene(scene, true);
-  if (st != DAVA_OK) return st;
-  int lds = 0;
-  const int as = sgd_adjoint_status(scene, config, &lds);
-  if (as != DAVA_OK) return as;
-  if (scene->batch == 0) return DAVA_OK;
-  if (!x_out_grad || !x0_grad) return DAVA_ERR_INVALID_ARGUMENT;
-  const int K = config->iterations, Pv = round_up(scene->num_parameters, 4);
-  if (K > 0 && (!tape || tape_bytes < sgd_tape_bytes(scene->batch, K, Pv))) return DAVA_ERR_WORKSPACE;
-  SgdAdjointArgs a;
-  a.L = make_layout(scene);
-  a.Pv = Pv;
-  a.K = K;
-  a.lr = config->learning_rate;
-  a.obs = scene->observations;
-  a.vis = scene->visibility;
-  a.tape = static_cast<const float*>(tape);
-  a.gout = x_out_grad;
-  a.gx0 = x0_grad;
-  a.gobs = observations_grad;
-  with_flag(scene->residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
-    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
-    launch_lds(sgd_ba_adjoint_kernel<kRes>, scene->batch, kBlock, lds, static_cast<hipStream_t>(stream), a);
-  });
-  return launched();
-}
-
-// host-only: 0, 1, 2, or minus the status
-extern "C" int dava_ba_sgd_backward_form(const DavaScene* scene, const DavaSgdConfig* config) {
-  const int st = check_scene(scene, false);
-  if (st != DAVA_OK) return -st;
-  const SgdAdjointLarge p = sgd_adjoint_large(scene, config, false);
-  return p.status == DAVA_OK ? p.form : -p.status;
-}
-
-// host-only; obs_grad: observations_grad will be asked for.  0: unsupported.
-extern "C" size_t dava_ba_sgd_backward_large_workspace_bytes(const DavaScene* scene, const DavaSgdConfig* config,
-                                                             int obs_grad) {
-  if (check_scene(scene, false) != DAVA_OK) return 0;
-  const SgdAdjointLarge p = sgd_adjoint_large(scene, config, obs_grad != 0);
-  return p.status == DAVA_OK ? p.workspace_bytes() : 0;
-}
-
-extern "C" int dava_ba_sgd_backward_large(const DavaScene* scene, const DavaSgdConfig* config, const void* tape,
-                                          size_t tape_bytes, const float* x_out_grad, float* x0_grad,
-                                          float* observations_grad, void* workspace, size_t workspace_bytes,
-                                          void* stream) {
-  const int st = check_scene(scene, true);
-  if (st != DAVA_OK) return st;
-  if (!config || config->iterations < 0) return DAVA_ERR_INVALID_ARGUMENT;
-  if (scene->batch == 0) return DAVA_OK;
-  if (!x_out_grad || !x0_grad) return DAVA_ERR_INVALID_ARGUMENT;
-  const SgdAdjointLarge p = sgd_adjoint_large(scene, config, observations_grad != nullptr);
-  if (p.status != DAVA_OK) return p.status;
-  const int K = config->iterations, Pv = round_up(scene->num_parameters, 4);
-  if (K > 0 && (!tape || tape_bytes < sgd_tape_bytes(scene->batch, K, Pv))) return DAVA_ERR_WORKSPACE;
+  if (st != DAVA_OK) return refuse(st);
+  p = sgd_adjoint_shape(scene, config, observations_grad != nullptr, any_form);
+  // (the symbol of the LDS image answers for its fit before the empty batch, the other one after the pointers)
+  if (p.status == DAVA_ERR_INVALID_ARGUMENT || (!any_form && p.status != DAVA_OK)) return p;
+  if (scene->batch == 0) return refuse(DAVA_OK);
+  if (!x_out_grad || !x0_grad) return refuse(DAVA_ERR_INVALID_ARGUMENT);
+  if (p.status != DAVA_OK) return p;
+  if (config->iterations > 0 && (!tape || tape_bytes < p.tape_bytes)) return refuse(DAVA_ERR_WORKSPACE);
   if (p.obsd_bytes + p.vector_bytes > 0 && (!workspace || workspace_bytes < p.workspace_bytes()))
-    return DAVA_ERR_WORKSPACE;
-  LargeSgdAdjointArgs a;
+    return refuse(DAVA_ERR_WORKSPACE);
+  LargeSgdAdjointArgs& a = p.args;
   a.L = make_layout(scene);
-  a.Pv = Pv;
-  a.K = K;
+  a.Pv = round_up(scene->num_parameters, 4);
+  a.K = config->iterations;
   a.lr = config->learning_rate;
   a.obs = scene->observations;
   a.vis = scene->visibility;
@@ -231,6 +171,66 @@ extern "C" int dava_ba_sgd_backward_large(const DavaScene* scene, const DavaSgdC
   a.gobs = observations_grad;
   a.obsd = p.obsd_bytes ? static_cast<float*>(workspace) : nullptr;
   a.vecs = p.form == 2 ? reinterpret_cast<float*>(static_cast<char*>(workspace) + p.obsd_bytes) : nullptr;
-  if (p.form == 0) return launch_sgd_adjoint<0>(a, scene, p.lds, stream);
-  return p.form == 1 ? launch_sgd_adjoint<1>(a, scene, p.lds, stream) : launch_sgd_adjoint<2>(a, scene, p.lds, stream);
+  p.launch = true;
+  return p;
+}
+
+template <int FORM>
+static int launch_sgd_adjoint(const SgdAdjointLaunch& p, const DavaScene* scene, void* stream) {
+  const sgd_adjoint_args_t<FORM>& a = p.args;
+  with_flag(scene->residual == DAVA_RESIDUAL_RAY_ANGLE, [&](auto ray) {
+    constexpr int kRes = decltype(ray)::value ? DAVA_RESIDUAL_RAY_ANGLE : DAVA_RESIDUAL_SQUARED_REPROJECTION;
+    launch_lds(sgd_ba_adjoint_kernel<kRes, FORM>, scene->batch, kBlock, p.lds, static_cast<hipStream_t>(stream), a);
+  });
+  return launched();
+}
+
+static int run_sgd_adjoint(const SgdAdjointLaunch& p, const DavaScene* scene, void* stream) {
+  if (!p.launch) return p.status;
+  if (p.form == 0) return launch_sgd_adjoint<0>(p, scene, stream);
+  return p.form == 1 ? launch_sgd_adjoint<1>(p, scene, stream) : launch_sgd_adjoint<2>(p, scene, stream);
+}
+
+// the shape behind a host-only query (which looks at no data pointer)
+static SgdAdjointLaunch sgd_adjoint_query(const DavaScene* scene, const DavaSgdConfig* config, bool obs_grad,
+                                          bool any_form) {
+  SgdAdjointLaunch p{};
+  p.status = check_scene(scene, false);
+  return p.status == DAVA_OK ? sgd_adjoint_shape(scene, config, obs_grad, any_form) : p;
+}
+
+}  // namespace dava
+
+using namespace dava;
+
+extern "C" int dava_ba_sgd_backward_supported(const DavaScene* scene, const DavaSgdConfig* config) {
+  return sgd_adjoint_query(scene, config, false, false).status == DAVA_OK ? 1 : 0;
+}
+
+extern "C" int dava_ba_sgd_backward(const DavaScene* scene, const DavaSgdConfig* config, const void* tape,
+                                    size_t tape_bytes, const float* x_out_grad, float* x0_grad,
+                                    float* observations_grad, void* stream) {
+  return run_sgd_adjoint(plan_sgd_adjoint(scene, config, tape, tape_bytes, x_out_grad, x0_grad, observations_grad,
+                                          nullptr, 0, false), scene, stream);
+}
+
+// host-only: 0, 1, 2, or minus the status
+extern "C" int dava_ba_sgd_backward_form(const DavaScene* scene, const DavaSgdConfig* config) {
+  const SgdAdjointLaunch p = sgd_adjoint_query(scene, config, false, true);
+  return p.status == DAVA_OK ? p.form : -p.status;
+}
+
+// host-only; obs_grad: observations_grad will be asked for.  0: unsupported.
+extern "C" size_t dava_ba_sgd_backward_large_workspace_bytes(const DavaScene* scene, const DavaSgdConfig* config,
+                                                             int obs_grad) {
+  const SgdAdjointLaunch p = sgd_adjoint_query(scene, config, obs_grad != 0, true);
+  return p.status == DAVA_OK ? p.workspace_bytes() : 0;
+}
+
+extern "C" int dava_ba_sgd_backward_large(const DavaScene* scene, const DavaSgdConfig* config, const void* tape,
+                                          size_t tape_bytes, const float* x_out_grad, float* x0_grad,
+                                          float* observations_grad, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  return run_sgd_adjoint(plan_sgd_adjoint(scene, config, tape, tape_bytes, x_out_grad, x0_grad, observations_grad,
+                                          workspace, workspace_bytes, true), scene, stream);
 }

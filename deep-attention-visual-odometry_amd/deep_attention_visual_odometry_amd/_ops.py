@@ -12,7 +12,7 @@ CPU kernel and no fallback.  Outputs a caller did not ask for come back as empty
 Ops never alias or mutate their inputs, except the Wolfe state machine's
 ``state``/``flags`` (declared in ``mutates_args``) and a caller-supplied workspace.
 """
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -101,6 +101,51 @@ def _require_float32(x: Tensor, what: str) -> None:
     if x.dtype != torch.float32:
         raise TypeError(f"{what} are float32 only (got {x.dtype}); the float64 flavour covers ba_solve and "
                         "ba_evaluate")
+
+
+def _require_float64(x: Tensor, what: str) -> None:
+    if x.dtype != torch.float64:
+        raise TypeError(f"{what} take float64 tensors (got {x.dtype})")
+
+
+def _same(t: Optional[Tensor], like: Tensor, dtype: torch.dtype, what: str) -> None:
+    """An optional operand a kernel reads with ``like``'s extents: its shape, its device, ``dtype``, contiguous."""
+    if t is not None and (t.shape != like.shape or t.dtype != dtype or t.device != like.device
+                          or not t.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous {_name(dtype)} tensor of shape {tuple(like.shape)} on "
+                         f"{like.device}")
+
+
+def _name(dtype: torch.dtype) -> str:
+    return str(dtype).split(".")[-1]  # "float32"
+
+
+def _scratch(need: int, dev) -> Tensor:
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    if _POISON:  # debugging aid: every byte the kernels do not write reads back as NaN
+        ws.fill_(0xFF)
+    return ws
+
+
+def sgd_config(learning_rate: float, iterations: int) -> N.DavaSgdConfig:
+    return N.DavaSgdConfig(float(learning_rate), int(iterations))
+
+
+def sgd_config_f64(learning_rate: float, iterations: int) -> N.DavaSgdConfigF64:
+    return N.DavaSgdConfigF64(float(learning_rate), int(iterations))
+
+
+class _Flavour(NamedTuple):
+    """What the float32 and the float64 operator of one schema differ in, besides their C symbols and refusals: the
+    factories below (second derivatives, gradient descent, its recording and its adjoint) write each body once."""
+    dtype: torch.dtype
+    scene: Callable      # scene_struct / scene_struct_f64
+    sgd_config: Callable
+    require: Callable    # (tensor, what): the TypeError of another dtype
+
+
+_F32 = _Flavour(torch.float32, scene_struct, sgd_config, _require_float32)
+_F64 = _Flavour(torch.float64, scene_struct_f64, sgd_config_f64, _require_float64)
 
 
 def f64_old_symbol_runs(probe) -> bool:
@@ -261,44 +306,77 @@ def _(x, observations, visibility, num_views, num_points, distortion, direction,
             x.new_empty((b,) if want_slope else (0,)))
 
 
-@torch.library.custom_op("dava::ba_second_order", mutates_args=(), device_types=_CUDA)
-def ba_second_order(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                    distortion: bool, direction: Optional[Tensor], residual: int, want_hv: bool,
-                    want_obs: bool, obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """``dava_ba_second_order_obs``: (E, dE/dx, H v + (d2E/dx dobs) u, dE/dobs, (d2E/dobs dx) v + (d2E/dobs2) u),
-    forward-over-reverse.  direction / obs_direction None mean v = 0 / u = 0.  Unrequested outputs are empty."""
-    lib = N.load_library()
-    _require_float32(x, "second derivatives of the fused objectives")
-    _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
-    if direction is not None and (direction.shape != x.shape or direction.dtype != torch.float32
-                                  or not direction.is_contiguous()):
-        raise ValueError("direction must be a contiguous float32 tensor of the parameters' shape")
-    if obs_direction is not None and (obs_direction.shape != observations.shape or obs_direction.dtype != torch.float32
-                                      or not obs_direction.is_contiguous()):
-        raise ValueError("obs_direction must be a contiguous float32 tensor of the observations' shape")
-    b = x.shape[0]
-    err = torch.empty(b, device=x.device, dtype=torch.float32)
-    grad = torch.empty_like(x)
-    hv = torch.empty_like(x) if want_hv else _empty0(x)
-    obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
-    obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
-    sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
-    with torch.cuda.device(x.device):
-        N.check(lib.dava_ba_second_order_obs(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err),
-                                             N.ptr(grad), N.ptr(hv) if want_hv else None,
-                                             N.ptr(obs_grad) if want_obs else None,
-                                             N.ptr(obs_hv) if (want_obs and want_hv) else None, N.stream_of(x.device)),
-                "dava_ba_second_order_obs")
-    return err, grad, hv, obs_grad, obs_hv
+# ---------------------------------------- second derivatives: float32, float64 and their `*_large` forms
+# One body and one fake kernel for the four operators.  ba_second_order and ba_second_order_f64 keep one problem's
+# whole dual image in LDS (160 KiB), keep their limits and ignore the form overrides; the `*_large` operators take
+# any admitted scene size (forms 1 and 2 beyond the LDS image; a scene whose image fits runs the launch of the first)
+# and differ in the C symbol, one scratch buffer from torch's allocator and the refusal text.
+
+def _second_order_op(name: str, doc: str, flavour: _Flavour, what: str, symbol: str = "",
+                     workspace_query: Optional[str] = None, refusal: str = ""):
+    symbol = symbol or f"dava_{name}"
+
+    @torch.library.custom_op(f"dava::{name}", mutates_args=(), device_types=_CUDA)
+    def op(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int, distortion: bool,
+           direction: Optional[Tensor], residual: int, want_hv: bool, want_obs: bool,
+           obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+        lib = N.load_library()
+        flavour.require(x, what)
+        _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
+        _same(direction, x, flavour.dtype, "direction")
+        _same(obs_direction, observations, flavour.dtype, "obs_direction")
+        b = x.shape[0]
+        err = torch.empty(b, device=x.device, dtype=flavour.dtype)
+        grad = torch.empty_like(x)
+        hv = torch.empty_like(x) if want_hv else _empty0(x)
+        obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
+        obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
+        sc = flavour.scene(observations, visibility, num_views, num_points, distortion, b, residual)
+        scratch = ()
+        if workspace_query:
+            need = int(getattr(lib, workspace_query)(sc, 1 if want_obs else 0))
+            if need == 0:
+                raise ValueError(refusal)
+            ws = _scratch(need, x.device)
+            scratch = (N.ptr(ws), ws.numel())
+        with torch.cuda.device(x.device):
+            N.check(getattr(lib, symbol)(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err), N.ptr(grad),
+                                         N.ptr(hv) if want_hv else None, N.ptr(obs_grad) if want_obs else None,
+                                         N.ptr(obs_hv) if (want_obs and want_hv) else None, *scratch,
+                                         N.stream_of(x.device)), symbol)
+        return err, grad, hv, obs_grad, obs_hv
+
+    op.__doc__ = doc
+    op.register_fake(_second_order_fake)
+    return op
 
 
-@ba_second_order.register_fake
-def _(x, observations, visibility, num_views, num_points, distortion, direction, residual, want_hv, want_obs,
-      obs_direction=None):
+def _second_order_fake(x, observations, visibility, num_views, num_points, distortion, direction, residual,
+                       want_hv, want_obs, obs_direction=None):
     b = x.shape[0]
     return (x.new_empty((b,)), torch.empty_like(x), torch.empty_like(x) if want_hv else x.new_empty((0,)),
             torch.empty_like(observations) if want_obs else x.new_empty((0,)),
             torch.empty_like(observations) if (want_obs and want_hv) else x.new_empty((0,)))
+
+
+ba_second_order = _second_order_op(
+    "ba_second_order",
+    """``dava_ba_second_order_obs``: (E, dE/dx, H v + (d2E/dx dobs) u, dE/dobs, (d2E/dobs dx) v + (d2E/dobs2) u),
+    forward-over-reverse.  direction / obs_direction None mean v = 0 / u = 0.  Unrequested outputs are empty.""",
+    _F32, "second derivatives of the fused objectives", "dava_ba_second_order_obs")
+ba_second_order_large = _second_order_op(
+    "ba_second_order_large", "``dava_ba_second_order_large``: ``ba_second_order`` for a scene of any size.",
+    _F32, "second derivatives of the fused objectives", "", "dava_ba_second_order_large_workspace_bytes",
+    "this scene has no float32 second derivatives (more views than the dual view constants can hold in LDS)")
+ba_second_order_f64 = _second_order_op(
+    "ba_second_order_f64",
+    "``dava_ba_second_order_f64``: ``ba_second_order`` on a float64 batch (dual numbers over double).",
+    _F64, "the float64 second derivatives")
+ba_second_order_large_f64 = _second_order_op(
+    "ba_second_order_large_f64",
+    "``dava_ba_second_order_large_f64``: ``ba_second_order_f64`` for a scene of any size.",
+    _F64, "the float64 second derivatives", "", "dava_ba_second_order_large_workspace_bytes_f64",
+    "this scene has no float64 second derivatives (more views than the dual view constants can hold in LDS)")
 
 
 @torch.library.custom_op("dava::ba_solve_record", mutates_args=(), device_types=_CUDA)
@@ -388,126 +466,217 @@ def _(x_out_grad, tape, status, observations, visibility, num_views, num_points,
             torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
 
 
-# ---------------------------------------- fused gradient descent (SGDSolver)
-
-def sgd_config(learning_rate: float, iterations: int) -> N.DavaSgdConfig:
-    return N.DavaSgdConfig(float(learning_rate), int(iterations))
-
+# ---------------------------------------- fused gradient descent (SGDSolver) and its adjoint
+# Three schemas -- the descent, the recording descent (an autograd node) and its adjoint -- each with one body, one
+# fake kernel and, for the node, one backward.  The float32 operators keep one problem's image in LDS and keep their
+# refusals; ba_sgd_solve_differentiable_large and ba_sgd_backward_large take any admitted scene size (forms 1 and 2
+# of csrc/ba_second_carve.hpp).  In float64 there is one operator per operation: the C symbols take forms 0, 1 and 2
+# themselves (csrc/sgd_solve_f64.hip, sgd_adjoint_f64.hip).  Workspaces come from torch's allocator, sized by the
+# library's host queries.
 
 def sgd_tape_rows(p: int) -> int:
     """Floats per tape row: round_up(P, 4) (csrc/sgd_plan.hpp)."""
     return (p + 3) // 4 * 4
 
 
-def _sgd_scene(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-               distortion: bool, learning_rate: float, iterations: int, residual: int, what: str):
-    _require_float32(x0, what)
+def _sgd_scene(flavour: _Flavour, x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
+               num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int, what: str):
+    flavour.require(x0, what)
     _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
     if iterations < 0:
         raise ValueError(f"iterations must be >= 0, got {iterations}")
-    sc = scene_struct(observations, visibility, num_views, num_points, distortion, x0.shape[0], residual)
-    return sc, sgd_config(learning_rate, iterations)
+    sc = flavour.scene(observations, visibility, num_views, num_points, distortion, x0.shape[0], residual)
+    return sc, flavour.sgd_config(learning_rate, iterations)
 
 
 _SGD_REFUSAL = ("this scene has no fused gradient descent: its image (x and the gradient, 2 round_up(P, 4) floats, "
                 "and the objective's view constants) does not fit one workgroup's 160 KiB of LDS")
+_SGD_REFUSAL_F64 = ("this scene has no float64 fused gradient descent: more views than the view constants can hold "
+                    "in one workgroup's 160 KiB of LDS")
+_SGD_ADJOINT_REFUSAL_F64 = ("this scene has no float64 fused adjoint of the gradient descent: more views than the "
+                            "dual view constants can hold in one workgroup's 160 KiB of LDS")
+_SGD_ADJOINT_REFUSAL_LARGE = ("this scene has no fused adjoint of the gradient descent: more views than the dual view "
+                              "constants can hold in LDS")
 
 
-@torch.library.custom_op("dava::ba_sgd_solve", mutates_args=(), device_types=_CUDA)
-def ba_sgd_solve(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                 distortion: bool, learning_rate: float, iterations: int, residual: int,
-                 want_errors: bool) -> Tuple[Tensor, Tensor]:
-    """``dava_ba_sgd_solve``: ``iterations`` steps x <- x - learning_rate dE/dx of a (B, P) fp32 batch in one
-    launch.  Returns (x, E(x_k) (B, iterations) or empty)."""
-    lib = N.load_library()
-    sc, cfg = _sgd_scene(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
-                         residual, "the fused gradient descent")
-    b, dev = x0.shape[0], x0.device
-    x_out = torch.empty_like(x0)
-    errs = torch.empty((b, iterations), device=dev, dtype=torch.float32) if want_errors else _empty0(x0)
-    with torch.cuda.device(dev):
-        status = lib.dava_ba_sgd_solve(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
-                                       N.stream_of(dev))
-    if status == N.DAVA_ERR_UNSUPPORTED:
-        raise ValueError(_SGD_REFUSAL)
-    N.check(status, "dava_ba_sgd_solve")
-    return x_out, errs
+def _sgd_solve_workspace_f64(lib, sc, cfg, dev):
+    """(tensor, pointer, bytes) of the descent's workspace: form 2's vectors, or (None, None, 0)."""
+    if lib.dava_ba_sgd_solve_form_f64(sc, cfg) < 0:
+        raise ValueError(_SGD_REFUSAL_F64)
+    need = int(lib.dava_ba_sgd_solve_workspace_bytes_f64(sc, cfg))
+    if need == 0:
+        return None, None, 0
+    ws = _scratch(need, dev)
+    return ws, N.ptr(ws), ws.numel()
 
 
-@ba_sgd_solve.register_fake
-def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
-      want_errors):
+def _sgd_solve_op(name: str, doc: str, flavour: _Flavour, what: str, workspace: bool):
+    """``workspace`` (float64): the form is asked before the launch and refuses there, and the symbol takes a
+    workspace; without it (float32) the launch's own ``DAVA_ERR_UNSUPPORTED`` is the refusal."""
+    symbol = f"dava_{name}"
+
+    @torch.library.custom_op(f"dava::{name}", mutates_args=(), device_types=_CUDA)
+    def op(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int, distortion: bool,
+           learning_rate: float, iterations: int, residual: int, want_errors: bool) -> Tuple[Tensor, Tensor]:
+        lib = N.load_library()
+        sc, cfg = _sgd_scene(flavour, x0, observations, visibility, num_views, num_points, distortion, learning_rate,
+                             iterations, residual, what)
+        b, dev = x0.shape[0], x0.device
+        scratch = ()
+        if workspace:
+            _ws, *scratch = _sgd_solve_workspace_f64(lib, sc, cfg, dev)
+        x_out = torch.empty_like(x0)
+        errs = torch.empty((b, iterations), device=dev, dtype=flavour.dtype) if want_errors else _empty0(x0)
+        with torch.cuda.device(dev):
+            status = getattr(lib, symbol)(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
+                                          *scratch, N.stream_of(dev))
+        if not workspace and status == N.DAVA_ERR_UNSUPPORTED:
+            raise ValueError(_SGD_REFUSAL)
+        N.check(status, symbol)
+        return x_out, errs
+
+    op.__doc__ = doc
+    op.register_fake(_sgd_solve_fake)
+    return op
+
+
+def _sgd_solve_fake(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+                    residual, want_errors):
     return torch.empty_like(x0), x0.new_empty((x0.shape[0], iterations) if want_errors else (0,))
 
 
-@torch.library.custom_op("dava::ba_sgd_solve_differentiable", mutates_args=(), device_types=_CUDA)
-def ba_sgd_solve_differentiable(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
-                                num_points: int, distortion: bool, learning_rate: float, iterations: int,
-                                residual: int, want_errors: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """``dava_ba_sgd_solve_record``: ``ba_sgd_solve`` (bitwise its x and errors) that also writes the tape
-    (B, iterations, round_up(P, 4)) of x_k.  An autograd node w.r.t. x0 and the observations: its backward is
-    ``ba_sgd_backward`` (not differentiable twice).  Returns (x, errors or empty, tape)."""
-    lib = N.load_library()
-    sc, cfg = _sgd_scene(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
-                         residual, "the recording gradient descent")
-    if not lib.dava_ba_sgd_backward_supported(sc, cfg):
-        raise ValueError("this scene has no fused adjoint of the gradient descent: its dual-number image must fit "
-                         "one workgroup's 160 KiB of LDS")
-    b, dev = x0.shape[0], x0.device
-    tape = torch.empty((b, iterations, sgd_tape_rows(x0.shape[1])), device=dev, dtype=torch.float32)
-    if _POISON:
-        tape.fill_(float("nan"))
-    x_out = torch.empty_like(x0)
-    errs = torch.empty((b, iterations), device=dev, dtype=torch.float32) if want_errors else _empty0(x0)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_sgd_solve_record(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
-                                             N.ptr(tape) if tape.numel() else None, tape.numel() * 4,
-                                             N.stream_of(dev)), "dava_ba_sgd_solve_record")
-    return x_out, errs, tape
+ba_sgd_solve = _sgd_solve_op(
+    "ba_sgd_solve",
+    """``dava_ba_sgd_solve``: ``iterations`` steps x <- x - learning_rate dE/dx of a (B, P) fp32 batch in one
+    launch.  Returns (x, E(x_k) (B, iterations) or empty).""",
+    _F32, "the fused gradient descent", workspace=False)
+ba_sgd_solve_f64 = _sgd_solve_op(
+    "ba_sgd_solve_f64",
+    """``dava_ba_sgd_solve_f64``: ``iterations`` steps x <- x - learning_rate dE/dx of a (B, P) float64 batch in
+    one launch, at any form.  Returns (x, E(x_k) (B, iterations) or empty).""",
+    _F64, "the float64 fused gradient descent", workspace=True)
 
 
-@ba_sgd_solve_differentiable.register_fake
-def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
-      want_errors):
-    b = x0.shape[0]
-    return (torch.empty_like(x0), x0.new_empty((b, iterations) if want_errors else (0,)),
-            x0.new_empty((b, iterations, sgd_tape_rows(x0.shape[1]))))
-
-
-def _check_sgd_tape(tape: Tensor, x_out_grad: Tensor, iterations: int) -> None:
+def _check_sgd_tape(tape: Tensor, x_out_grad: Tensor, iterations: int, dtype: torch.dtype) -> None:
     """The kernel dereferences the tape as device memory of this launch: refuse anything else loudly."""
     b, dev = x_out_grad.shape[0], x_out_grad.device
-    if (tape.device != dev or tape.dtype != torch.float32 or not tape.is_contiguous()
+    if (tape.device != dev or tape.dtype != dtype or not tape.is_contiguous()
             or tuple(tape.shape) != (b, iterations, sgd_tape_rows(x_out_grad.shape[1]))):
-        raise ValueError(f"tape must be the recording call's contiguous float32 ({b}, {iterations}, "
+        raise ValueError(f"tape must be the recording call's contiguous {_name(dtype)} ({b}, {iterations}, "
                          f"{sgd_tape_rows(x_out_grad.shape[1])}) tensor on {dev}, got {tuple(tape.shape)} "
                          f"{tape.dtype} on {tape.device}")
 
 
-@torch.library.custom_op("dava::ba_sgd_backward", mutates_args=(), device_types=_CUDA)
-def ba_sgd_backward(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
-                    num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int,
-                    want_observations: bool) -> Tuple[Tensor, Tensor]:
-    """``dava_ba_sgd_backward``: (dL/dx0, dL/dobs or empty) of a recorded descent for dL/dx_out."""
-    lib = N.load_library()
-    sc, cfg = _sgd_scene(x_out_grad, observations, visibility, num_views, num_points, distortion, learning_rate,
-                         iterations, residual, "the gradient descent's adjoint")
-    dev = x_out_grad.device
-    _check_sgd_tape(tape, x_out_grad, iterations)
-    gx = torch.empty_like(x_out_grad)
-    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_sgd_backward(sc, cfg, N.ptr(tape) if tape.numel() else None, tape.numel() * 4,
+def _sgd_backward_op(name: str, doc: str, flavour: _Flavour, what: str, workspace_query: Optional[str] = None,
+                     form_query: Optional[str] = None, refusal: str = ""):
+    """``refusal`` is raised where ``form_query`` answers < 0; without a form query, where ``workspace_query`` answers
+    0 bytes (with one, 0 bytes mean a ``NULL`` workspace)."""
+    symbol = f"dava_{name}"
+
+    @torch.library.custom_op(f"dava::{name}", mutates_args=(), device_types=_CUDA)
+    def op(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
+           num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int,
+           want_observations: bool) -> Tuple[Tensor, Tensor]:
+        lib = N.load_library()
+        sc, cfg = _sgd_scene(flavour, x_out_grad, observations, visibility, num_views, num_points, distortion,
+                             learning_rate, iterations, residual, what)
+        dev = x_out_grad.device
+        _check_sgd_tape(tape, x_out_grad, iterations, flavour.dtype)
+        if form_query and getattr(lib, form_query)(sc, cfg) < 0:
+            raise ValueError(refusal)
+        scratch = ()
+        if workspace_query:
+            need = int(getattr(lib, workspace_query)(sc, cfg, 1 if want_observations else 0))
+            if need == 0 and not form_query:
+                raise ValueError(refusal)
+            ws = _scratch(need, dev) if need else None
+            scratch = (N.ptr(ws), need)
+        gx = torch.empty_like(x_out_grad)
+        gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
+        with torch.cuda.device(dev):
+            N.check(getattr(lib, symbol)(sc, cfg, N.ptr(tape) if tape.numel() else None, tape.nbytes,
                                          N.ptr(x_out_grad), N.ptr(gx), N.ptr(gobs) if want_observations else None,
-                                         N.stream_of(dev)), "dava_ba_sgd_backward")
-    return gx, gobs
+                                         *scratch, N.stream_of(dev)), symbol)
+        return gx, gobs
+
+    op.__doc__ = doc
+    op.register_fake(_sgd_backward_fake)
+    return op
 
 
-@ba_sgd_backward.register_fake
-def _(x_out_grad, tape, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
-      residual, want_observations):
+def _sgd_backward_fake(x_out_grad, tape, observations, visibility, num_views, num_points, distortion, learning_rate,
+                       iterations, residual, want_observations):
     return (torch.empty_like(x_out_grad),
             torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
+
+
+ba_sgd_backward = _sgd_backward_op(
+    "ba_sgd_backward",
+    "``dava_ba_sgd_backward``: (dL/dx0, dL/dobs or empty) of a recorded descent for dL/dx_out.",
+    _F32, "the gradient descent's adjoint")
+ba_sgd_backward_large = _sgd_backward_op(
+    "ba_sgd_backward_large", "``dava_ba_sgd_backward_large``: ``ba_sgd_backward`` for a scene of any size.",
+    _F32, "the gradient descent's adjoint", "dava_ba_sgd_backward_large_workspace_bytes",
+    refusal=_SGD_ADJOINT_REFUSAL_LARGE)
+ba_sgd_backward_f64 = _sgd_backward_op(
+    "ba_sgd_backward_f64",
+    "``dava_ba_sgd_backward_f64``: (dL/dx0, dL/dobs or empty) of a recorded float64 descent for dL/dx_out.",
+    _F64, "the float64 gradient descent's adjoint", "dava_ba_sgd_backward_workspace_bytes_f64",
+    "dava_ba_sgd_backward_form_f64", _SGD_ADJOINT_REFUSAL_F64)
+
+
+def _sgd_record_op(name: str, doc: str, flavour: _Flavour, what: str, symbol: str, adjoint, has_adjoint,
+                   refusal: str, unsupported_is_refusal: bool = False, workspace: bool = False):
+    """``has_adjoint(lib, scene, config)`` is asked before anything is allocated and ``refusal`` raised where it is
+    false; ``adjoint`` is the operator the backward calls.  ``unsupported_is_refusal``: the launch's
+    ``DAVA_ERR_UNSUPPORTED`` becomes ``_SGD_REFUSAL``.  ``workspace``: the forward's, as in :func:`_sgd_solve_op`."""
+
+    @torch.library.custom_op(f"dava::{name}", mutates_args=(), device_types=_CUDA)
+    def op(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int, distortion: bool,
+           learning_rate: float, iterations: int, residual: int, want_errors: bool) -> Tuple[Tensor, Tensor, Tensor]:
+        lib = N.load_library()
+        sc, cfg = _sgd_scene(flavour, x0, observations, visibility, num_views, num_points, distortion, learning_rate,
+                             iterations, residual, what)
+        if not has_adjoint(lib, sc, cfg):
+            raise ValueError(refusal)
+        b, dev = x0.shape[0], x0.device
+        scratch = ()
+        if workspace:
+            _ws, *scratch = _sgd_solve_workspace_f64(lib, sc, cfg, dev)
+        tape = torch.empty((b, iterations, sgd_tape_rows(x0.shape[1])), device=dev, dtype=flavour.dtype)
+        if _POISON:
+            tape.fill_(float("nan"))
+        x_out = torch.empty_like(x0)
+        errs = torch.empty((b, iterations), device=dev, dtype=flavour.dtype) if want_errors else _empty0(x0)
+        with torch.cuda.device(dev):
+            status = getattr(lib, symbol)(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
+                                          N.ptr(tape) if tape.numel() else None, tape.nbytes, *scratch,
+                                          N.stream_of(dev))
+        if unsupported_is_refusal and status == N.DAVA_ERR_UNSUPPORTED:
+            raise ValueError(_SGD_REFUSAL)
+        N.check(status, symbol)
+        return x_out, errs, tape
+
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, x_grad, _errors_grad, _tape_grad):
+        tape, observations, visibility = ctx.saved_tensors
+        need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        x_grad = x_grad.to(flavour.dtype)
+        gx, gobs = adjoint(x_grad if x_grad.is_contiguous() else x_grad.contiguous(), tape, observations.detach(),
+                           visibility, *ctx.meta, bool(need_obs))
+        return (gx if need_x else None, gobs if need_obs else None) + (None,) * 8
+
+    op.__doc__ = doc
+    op.register_fake(_sgd_record_fake)
+    op.register_autograd(backward, setup_context=_sgd_setup_context)
+    return op
+
+
+def _sgd_record_fake(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+                     residual, want_errors):
+    b = x0.shape[0]
+    return (torch.empty_like(x0), x0.new_empty((b, iterations) if want_errors else (0,)),
+            x0.new_empty((b, iterations, sgd_tape_rows(x0.shape[1]))))
 
 
 def _sgd_setup_context(ctx, inputs, output):
@@ -516,238 +685,44 @@ def _sgd_setup_context(ctx, inputs, output):
     ctx.meta = (num_views, num_points, distortion, learning_rate, iterations, residual)
 
 
-@torch.autograd.function.once_differentiable
-def _sgd_backward(ctx, x_grad, _errors_grad, _tape_grad):
-    tape, observations, visibility = ctx.saved_tensors
-    need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    x_grad = x_grad.to(torch.float32)
-    gx, gobs = ba_sgd_backward(x_grad if x_grad.is_contiguous() else x_grad.contiguous(), tape, observations.detach(),
-                               visibility, *ctx.meta, bool(need_obs))
-    return (gx if need_x else None, gobs if need_obs else None) + (None,) * 8
+ba_sgd_solve_differentiable = _sgd_record_op(
+    "ba_sgd_solve_differentiable",
+    """``dava_ba_sgd_solve_record``: ``ba_sgd_solve`` (bitwise its x and errors) that also writes the tape
+    (B, iterations, round_up(P, 4)) of x_k.  An autograd node w.r.t. x0 and the observations: its backward is
+    ``ba_sgd_backward`` (not differentiable twice).  Returns (x, errors or empty, tape).""",
+    _F32, "the recording gradient descent", "dava_ba_sgd_solve_record", ba_sgd_backward,
+    lambda lib, sc, cfg: lib.dava_ba_sgd_backward_supported(sc, cfg),
+    "this scene has no fused adjoint of the gradient descent: its dual-number image must fit one workgroup's 160 KiB "
+    "of LDS")
+ba_sgd_solve_differentiable_large = _sgd_record_op(
+    "ba_sgd_solve_differentiable_large",
+    """``ba_sgd_solve_differentiable`` for a scene of any size the recording descent runs: the same recording
+    launch and tape; its backward is ``ba_sgd_backward_large`` (not differentiable twice).""",
+    _F32, "the recording gradient descent", "dava_ba_sgd_solve_record", ba_sgd_backward_large,
+    lambda lib, sc, cfg: lib.dava_ba_sgd_backward_form(sc, cfg) >= 0, _SGD_ADJOINT_REFUSAL_LARGE,
+    unsupported_is_refusal=True)
+ba_sgd_solve_differentiable_f64 = _sgd_record_op(
+    "ba_sgd_solve_differentiable_f64",
+    """``dava_ba_sgd_solve_record_f64``: ``ba_sgd_solve_f64`` (bitwise its x and errors) that also writes the tape
+    (B, iterations, round_up(P, 4)) of x_k in float64.  An autograd node w.r.t. x0 and the observations: its backward
+    is ``ba_sgd_backward_f64`` (not differentiable twice).  Returns (x, errors or empty, tape).""",
+    _F64, "the float64 recording gradient descent", "dava_ba_sgd_solve_record_f64", ba_sgd_backward_f64,
+    lambda lib, sc, cfg: lib.dava_ba_sgd_backward_form_f64(sc, cfg) >= 0, _SGD_ADJOINT_REFUSAL_F64, workspace=True)
 
 
-ba_sgd_solve_differentiable.register_autograd(_sgd_backward, setup_context=_sgd_setup_context)
-
-
-# ---------------------------------------- float32 dual-number kernels beyond the LDS image
-# ba_second_order, ba_sgd_solve_differentiable and ba_sgd_backward keep one problem's dual image in LDS and keep
-# their refusals; the `*_large` operators take any admitted scene size (forms 1 and 2 of csrc/ba_second_carve.hpp,
-# form 0's launch where it fits and no F32_DUAL_FORM override is set), with a workspace from torch's allocator sized
-# by the library's host queries.
+# ---------------------------------------- routing between an operator and its `*_large` form
 
 def f32_old_symbol_runs(probe) -> bool:
     """:func:`f64_old_symbol_runs` for the float32 dual-number kernels and their F32_DUAL_FORM override."""
     return N.library_knob("F32_DUAL_FORM") <= 0 and bool(probe())
 
 
-def _same_f32(t: Optional[Tensor], like: Tensor, what: str) -> None:
-    if t is not None and (t.shape != like.shape or t.dtype != torch.float32 or t.device != like.device
-                          or not t.is_contiguous()):
-        raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(like.shape)} on {like.device}")
-
-
-@torch.library.custom_op("dava::ba_second_order_large", mutates_args=(), device_types=_CUDA)
-def ba_second_order_large(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                          distortion: bool, direction: Optional[Tensor], residual: int, want_hv: bool,
-                          want_obs: bool,
-                          obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """``dava_ba_second_order_large``: ``ba_second_order`` for a scene of any size."""
-    lib = N.load_library()
-    _require_float32(x, "second derivatives of the fused objectives")
-    _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
-    _same_f32(direction, x, "direction")
-    _same_f32(obs_direction, observations, "obs_direction")
-    b = x.shape[0]
-    err = torch.empty(b, device=x.device, dtype=torch.float32)
-    grad = torch.empty_like(x)
-    hv = torch.empty_like(x) if want_hv else _empty0(x)
-    obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
-    obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
-    sc = scene_struct(observations, visibility, num_views, num_points, distortion, b, residual)
-    need = int(lib.dava_ba_second_order_large_workspace_bytes(sc, 1 if want_obs else 0))
-    if need == 0:
-        raise ValueError("this scene has no float32 second derivatives (more views than the dual view constants "
-                         "can hold in LDS)")
-    ws = _scratch(need, x.device)
-    with torch.cuda.device(x.device):
-        N.check(lib.dava_ba_second_order_large(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err),
-                                               N.ptr(grad), N.ptr(hv) if want_hv else None,
-                                               N.ptr(obs_grad) if want_obs else None,
-                                               N.ptr(obs_hv) if (want_obs and want_hv) else None, N.ptr(ws),
-                                               ws.numel(), N.stream_of(x.device)), "dava_ba_second_order_large")
-    return err, grad, hv, obs_grad, obs_hv
-
-
-@ba_second_order_large.register_fake
-def _(x, observations, visibility, num_views, num_points, distortion, direction, residual, want_hv, want_obs,
-      obs_direction=None):
-    b = x.shape[0]
-    return (x.new_empty((b,)), torch.empty_like(x), torch.empty_like(x) if want_hv else x.new_empty((0,)),
-            torch.empty_like(observations) if want_obs else x.new_empty((0,)),
-            torch.empty_like(observations) if (want_obs and want_hv) else x.new_empty((0,)))
-
-
-@torch.library.custom_op("dava::ba_sgd_solve_differentiable_large", mutates_args=(), device_types=_CUDA)
-def ba_sgd_solve_differentiable_large(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
-                                      num_points: int, distortion: bool, learning_rate: float, iterations: int,
-                                      residual: int, want_errors: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """``ba_sgd_solve_differentiable`` for a scene of any size the recording descent runs: the same recording
-    launch and tape; its backward is ``ba_sgd_backward_large`` (not differentiable twice)."""
-    lib = N.load_library()
-    sc, cfg = _sgd_scene(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
-                         residual, "the recording gradient descent")
-    if lib.dava_ba_sgd_backward_form(sc, cfg) < 0:
-        raise ValueError("this scene has no fused adjoint of the gradient descent: more views than the dual view "
-                         "constants can hold in LDS")
-    b, dev = x0.shape[0], x0.device
-    tape = torch.empty((b, iterations, sgd_tape_rows(x0.shape[1])), device=dev, dtype=torch.float32)
-    if _POISON:
-        tape.fill_(float("nan"))
-    x_out = torch.empty_like(x0)
-    errs = torch.empty((b, iterations), device=dev, dtype=torch.float32) if want_errors else _empty0(x0)
-    with torch.cuda.device(dev):
-        status = lib.dava_ba_sgd_solve_record(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
-                                              N.ptr(tape) if tape.numel() else None, tape.numel() * 4,
-                                              N.stream_of(dev))
-    if status == N.DAVA_ERR_UNSUPPORTED:
-        raise ValueError(_SGD_REFUSAL)
-    N.check(status, "dava_ba_sgd_solve_record")
-    return x_out, errs, tape
-
-
-@ba_sgd_solve_differentiable_large.register_fake
-def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
-      want_errors):
-    b = x0.shape[0]
-    return (torch.empty_like(x0), x0.new_empty((b, iterations) if want_errors else (0,)),
-            x0.new_empty((b, iterations, sgd_tape_rows(x0.shape[1]))))
-
-
-@torch.library.custom_op("dava::ba_sgd_backward_large", mutates_args=(), device_types=_CUDA)
-def ba_sgd_backward_large(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
-                          num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int,
-                          want_observations: bool) -> Tuple[Tensor, Tensor]:
-    """``dava_ba_sgd_backward_large``: ``ba_sgd_backward`` for a scene of any size."""
-    lib = N.load_library()
-    sc, cfg = _sgd_scene(x_out_grad, observations, visibility, num_views, num_points, distortion, learning_rate,
-                         iterations, residual, "the gradient descent's adjoint")
-    dev = x_out_grad.device
-    _check_sgd_tape(tape, x_out_grad, iterations)
-    need = int(lib.dava_ba_sgd_backward_large_workspace_bytes(sc, cfg, 1 if want_observations else 0))
-    if need == 0:
-        raise ValueError("this scene has no fused adjoint of the gradient descent: more views than the dual view "
-                         "constants can hold in LDS")
-    ws = _scratch(need, dev)
-    gx = torch.empty_like(x_out_grad)
-    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_sgd_backward_large(sc, cfg, N.ptr(tape) if tape.numel() else None, tape.numel() * 4,
-                                               N.ptr(x_out_grad), N.ptr(gx),
-                                               N.ptr(gobs) if want_observations else None, N.ptr(ws), ws.numel(),
-                                               N.stream_of(dev)), "dava_ba_sgd_backward_large")
-    return gx, gobs
-
-
-@ba_sgd_backward_large.register_fake
-def _(x_out_grad, tape, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
-      residual, want_observations):
-    return (torch.empty_like(x_out_grad),
-            torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
-
-
-@torch.autograd.function.once_differentiable
-def _sgd_backward_large(ctx, x_grad, _errors_grad, _tape_grad):
-    tape, observations, visibility = ctx.saved_tensors
-    need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    x_grad = x_grad.to(torch.float32)
-    gx, gobs = ba_sgd_backward_large(x_grad if x_grad.is_contiguous() else x_grad.contiguous(), tape,
-                                     observations.detach(), visibility, *ctx.meta, bool(need_obs))
-    return (gx if need_x else None, gobs if need_obs else None) + (None,) * 8
-
-
-ba_sgd_solve_differentiable_large.register_autograd(_sgd_backward_large, setup_context=_sgd_setup_context)
-
-
-# ---------------------------------------- float64 second derivatives, recording solve and adjoint
-# Operators of their own: ba_second_order, ba_solve_record and ba_solve_backward stay float32 only.  Each comes as
-# a pair with one body and one fake kernel: `*_f64` keeps one problem's whole image in LDS (160 KiB), keeps its
-# limits and error texts and ignores the F64_FORM override; `*_large_f64` takes any scene size (forms 1 and 2 beyond
-# the LDS image; a scene whose image fits runs the launch of the first) and differs in the C symbols, one scratch
-# buffer and the refusal text.
-
-def _require_float64(x: Tensor, what: str) -> None:
-    if x.dtype != torch.float64:
-        raise TypeError(f"{what} take float64 tensors (got {x.dtype})")
-
-
-def _same_f64(t: Optional[Tensor], like: Tensor, what: str) -> None:
-    if t is not None and (t.shape != like.shape or t.dtype != torch.float64 or t.device != like.device
-                          or not t.is_contiguous()):
-        raise ValueError(f"{what} must be a contiguous float64 tensor of shape {tuple(like.shape)} on {like.device}")
-
-
-def _scratch(need: int, dev) -> Tensor:
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    if _POISON:  # debugging aid: every byte the kernels do not write reads back as NaN
-        ws.fill_(0xFF)
-    return ws
-
-
-def _second_order_f64_op(name: str, doc: str, workspace_query: Optional[str] = None, refusal: str = ""):
-    symbol = f"dava_{name}"
-
-    @torch.library.custom_op(f"dava::{name}", mutates_args=(), device_types=_CUDA)
-    def op(x: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int, distortion: bool,
-           direction: Optional[Tensor], residual: int, want_hv: bool, want_obs: bool,
-           obs_direction: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-        lib = N.load_library()
-        _require_float64(x, "the float64 second derivatives")
-        _check_scene_tensors(x, observations, visibility, num_views, num_points, distortion)
-        _same_f64(direction, x, "direction")
-        _same_f64(obs_direction, observations, "obs_direction")
-        b = x.shape[0]
-        err = torch.empty(b, device=x.device, dtype=torch.float64)
-        grad = torch.empty_like(x)
-        hv = torch.empty_like(x) if want_hv else _empty0(x)
-        obs_grad = torch.empty_like(observations) if want_obs else _empty0(x)
-        obs_hv = torch.empty_like(observations) if (want_obs and want_hv) else _empty0(x)
-        sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, b, residual)
-        scratch = ()
-        if workspace_query:
-            need = int(getattr(lib, workspace_query)(sc, 1 if want_obs else 0))
-            if need == 0:
-                raise ValueError(refusal)
-            ws = _scratch(need, x.device)
-            scratch = (N.ptr(ws), ws.numel())
-        with torch.cuda.device(x.device):
-            N.check(getattr(lib, symbol)(sc, N.ptr(x), N.ptr(direction), N.ptr(obs_direction), N.ptr(err), N.ptr(grad),
-                                         N.ptr(hv) if want_hv else None, N.ptr(obs_grad) if want_obs else None,
-                                         N.ptr(obs_hv) if (want_obs and want_hv) else None, *scratch,
-                                         N.stream_of(x.device)), symbol)
-        return err, grad, hv, obs_grad, obs_hv
-
-    op.__doc__ = doc
-    op.register_fake(_second_order_f64_fake)
-    return op
-
-
-def _second_order_f64_fake(x, observations, visibility, num_views, num_points, distortion, direction, residual,
-                           want_hv, want_obs, obs_direction=None):
-    b = x.shape[0]
-    return (x.new_empty((b,)), torch.empty_like(x), torch.empty_like(x) if want_hv else x.new_empty((0,)),
-            torch.empty_like(observations) if want_obs else x.new_empty((0,)),
-            torch.empty_like(observations) if (want_obs and want_hv) else x.new_empty((0,)))
-
-
-ba_second_order_f64 = _second_order_f64_op(
-    "ba_second_order_f64",
-    "``dava_ba_second_order_f64``: ``ba_second_order`` on a float64 batch (dual numbers over double).")
-ba_second_order_large_f64 = _second_order_f64_op(
-    "ba_second_order_large_f64",
-    "``dava_ba_second_order_large_f64``: ``ba_second_order_f64`` for a scene of any size.",
-    "dava_ba_second_order_large_workspace_bytes_f64",
-    "this scene has no float64 second derivatives (more views than the dual view constants can hold in LDS)")
-
+# ---------------------------------------- float64 recording solve and adjoint
+# Operators of their own: ba_solve_record and ba_solve_backward stay float32 only.  Each comes as a pair with one
+# body and one fake kernel: `*_f64` keeps one problem's whole image in LDS (160 KiB), keeps its limits and error
+# texts and ignores the F64_FORM override; `*_large_f64` takes any scene size (forms 1 and 2 beyond the LDS image; a
+# scene whose image fits runs the launch of the first) and differs in the C symbols, one scratch buffer and the
+# refusal text.
 
 def tape_bytes_f64(batch: int, p: int, iterations: int) -> int:
     """csrc/dava_tape.hpp's layout with 8-byte elements (what ``dava_ba_solve_tape_bytes_f64`` returns where the
@@ -902,7 +877,7 @@ def _row_batch(t: Tensor, what: str) -> Tuple[int, int]:
     return t.shape[0], t.shape[1]
 
 
-def _same(t: Tensor, like: Tensor, shape, what: str) -> None:
+def _expect(t: Tensor, like: Tensor, shape, what: str) -> None:
     if tuple(t.shape) != tuple(shape) or t.dtype != like.dtype or t.device != like.device or not t.is_contiguous():
         raise ValueError(f"{what}: expected contiguous {like.dtype} {tuple(shape)} on {like.device}, "
                          f"got {t.dtype} {tuple(t.shape)} on {t.device}")
@@ -912,8 +887,8 @@ def _same(t: Tensor, like: Tensor, shape, what: str) -> None:
 def bfgs_update_inverse_hessian(h: Tensor, s: Tensor, y: Tensor) -> Tensor:
     """(B, n, n), (B, n), (B, n) -> H+ (``bfgs_solver.py:235-303``)."""
     b, n = _square_batch(h)
-    _same(s, h, (b, n), "step")
-    _same(y, h, (b, n), "delta_gradient")
+    _expect(s, h, (b, n), "step")
+    _expect(y, h, (b, n), "delta_gradient")
     out = torch.empty_like(h)
     with torch.cuda.device(h.device):
         N.check(getattr(N.load_library(), f"dava_bfgs_update_inverse_hessian_{_dt(h)}")(
@@ -933,7 +908,7 @@ _UPDATE_BACKWARD_VECTORS, _UPDATE_BACKWARD_LDS_BYTES = 9, 150 * 1024  # update_b
 def bfgs_update_inverse_hessian_backward(h: Tensor, s: Tensor, y: Tensor, grad: Tensor, need_h: bool, need_s: bool,
                                          need_y: bool) -> Tuple[Tensor, Tensor, Tensor]:
     b, n = _square_batch(h)
-    _same(grad, h, (b, n, n), "grad")
+    _expect(grad, h, (b, n, n), "grad")
     gh = torch.empty_like(h) if need_h else _empty0(h)
     gs = torch.empty_like(s) if need_s else _empty0(h)
     gy = torch.empty_like(y) if need_y else _empty0(h)
@@ -965,7 +940,7 @@ def _(h, s, y, grad, need_h, need_s, need_y):
 def bfgs_initial_scale(s: Tensor, y: Tensor) -> Tensor:
     """(B, n), (B, n) -> gamma (B,) (``bfgs_solver.py:217-233``)."""
     b, n = _row_batch(s, "step")
-    _same(y, s, (b, n), "delta_gradient")
+    _expect(y, s, (b, n), "delta_gradient")
     out = s.new_empty((b,))
     with torch.cuda.device(s.device):
         N.check(getattr(N.load_library(), f"dava_bfgs_initial_scale_{_dt(s)}")(
@@ -982,7 +957,7 @@ def _(s, y):
 def bfgs_initial_scale_backward(s: Tensor, y: Tensor, grad: Tensor, need_s: bool,
                                 need_y: bool) -> Tuple[Tensor, Tensor]:
     b, n = _row_batch(s, "step")
-    _same(grad, s, (b,), "grad")
+    _expect(grad, s, (b,), "grad")
     gs = torch.empty_like(s) if need_s else _empty0(s)
     gy = torch.empty_like(y) if need_y else _empty0(s)
     with torch.cuda.device(s.device):
@@ -1001,7 +976,7 @@ def _(s, y, grad, need_s, need_y):
 def bfgs_scale_matrix(scale: Tensor, h: Tensor) -> Tensor:
     """scale (B,) * H (B, n, n): the k == 1 rescale of H0 (``bfgs_solver.py:159-167``)."""
     b, n = _square_batch(h)
-    _same(scale, h, (b,), "scale")
+    _expect(scale, h, (b,), "scale")
     out = torch.empty_like(h)
     with torch.cuda.device(h.device):
         N.check(getattr(N.load_library(), f"dava_bfgs_scale_matrix_{_dt(h)}")(
@@ -1018,7 +993,7 @@ def _(scale, h):
 def bfgs_scale_matrix_backward(scale: Tensor, h: Tensor, grad: Tensor, need_scale: bool,
                                need_h: bool) -> Tuple[Tensor, Tensor]:
     b, n = _square_batch(h)
-    _same(grad, h, (b, n, n), "grad")
+    _expect(grad, h, (b, n, n), "grad")
     gsc = torch.empty_like(scale) if need_scale else _empty0(h)
     gh = torch.empty_like(h) if need_h else _empty0(h)
     with torch.cuda.device(h.device):
@@ -1038,7 +1013,7 @@ def _(scale, h, grad, need_scale, need_h):
 def bfgs_search_direction(h: Tensor, g: Tensor) -> Tensor:
     """d = -H g (``bfgs_solver.py:173-176``)."""
     b, n = _square_batch(h)
-    _same(g, h, (b, n), "gradient")
+    _expect(g, h, (b, n), "gradient")
     out = torch.empty_like(g)
     with torch.cuda.device(h.device):
         N.check(getattr(N.load_library(), f"dava_bfgs_search_direction_{_dt(h)}")(
@@ -1059,8 +1034,8 @@ def bfgs_compact_direction(g: Tensor, y: Tensor, s: Tensor, problem_index: Tenso
     """The generic loop's update + search direction on compact history rows (no dense matrix): appends
     entry ``count`` to the history of the problems ``problem_index`` and returns d = -H g (n_active, P)."""
     n_act, p = _row_batch(g, "gradient")
-    _same(y, g, (n_act, p), "delta_gradient")
-    _same(s, g, (n_act, p), "step")
+    _expect(y, g, (n_act, p), "delta_gradient")
+    _expect(s, g, (n_act, p), "step")
     if problem_index.dtype != torch.int64 or tuple(problem_index.shape) != (n_act,) \
             or problem_index.device != g.device or not problem_index.is_contiguous():
         raise ValueError("problem_index must be a contiguous int64 (n_active,) tensor on the gradient's device")
@@ -1095,7 +1070,7 @@ def _(g, y, s, problem_index, count, history_s, history_w, history_rho, history_
 def bfgs_search_direction_backward(h: Tensor, g: Tensor, grad: Tensor, need_h: bool,
                                    need_g: bool) -> Tuple[Tensor, Tensor]:
     b, n = _square_batch(h)
-    _same(grad, h, (b, n), "grad")
+    _expect(grad, h, (b, n), "grad")
     gh = torch.empty_like(h) if need_h else _empty0(h)
     gg = torch.empty_like(g) if need_g else _empty0(h)
     with torch.cuda.device(h.device):
@@ -1120,8 +1095,8 @@ WOLFE_FLAG_COLUMNS = 2
 def wolfe_init(direction: Tensor, f0: Tensor, g0: Tensor) -> Tuple[Tensor, Tensor]:
     """(state (B, 9), flags (B, 2) uint8) for a line search along ``direction`` from (f0, g0)."""
     b, n = _row_batch(direction, "search_direction")
-    _same(g0, direction, (b, n), "base_gradient")
-    _same(f0, direction, (b,), "base_error")
+    _expect(g0, direction, (b, n), "base_gradient")
+    _expect(f0, direction, (b,), "base_error")
     state = direction.new_empty((b, WOLFE_STATE_COLUMNS))
     flags = direction.new_empty((b, WOLFE_FLAG_COLUMNS), dtype=torch.uint8)
     with torch.cuda.device(direction.device):
@@ -1192,8 +1167,8 @@ def _cpu_ptr(t: Optional[Tensor]):
 @bfgs_update_inverse_hessian.register_kernel("cpu")
 def _(h, s, y):
     b, n = _square_batch(h)
-    _same(s, h, (b, n), "step")
-    _same(y, h, (b, n), "delta_gradient")
+    _expect(s, h, (b, n), "step")
+    _expect(y, h, (b, n), "delta_gradient")
     out = torch.empty_like(h)
     _cpu("bfgs_update_inverse_hessian", h, b, n, N.ptr(h), N.ptr(s), N.ptr(y), N.ptr(out))
     return out
@@ -1202,7 +1177,7 @@ def _(h, s, y):
 @bfgs_update_inverse_hessian_backward.register_kernel("cpu")
 def _(h, s, y, grad, need_h, need_s, need_y):
     b, n = _square_batch(h)
-    _same(grad, h, (b, n, n), "grad")
+    _expect(grad, h, (b, n, n), "grad")
     gh = torch.empty_like(h) if need_h else _empty0(h)
     gs = torch.empty_like(s) if need_s else _empty0(h)
     gy = torch.empty_like(y) if need_y else _empty0(h)
@@ -1214,7 +1189,7 @@ def _(h, s, y, grad, need_h, need_s, need_y):
 @bfgs_initial_scale.register_kernel("cpu")
 def _(s, y):
     b, n = _row_batch(s, "step")
-    _same(y, s, (b, n), "delta_gradient")
+    _expect(y, s, (b, n), "delta_gradient")
     out = s.new_empty((b,))
     _cpu("bfgs_initial_scale", s, b, n, N.ptr(s), N.ptr(y), N.ptr(out))
     return out
@@ -1223,7 +1198,7 @@ def _(s, y):
 @bfgs_initial_scale_backward.register_kernel("cpu")
 def _(s, y, grad, need_s, need_y):
     b, n = _row_batch(s, "step")
-    _same(grad, s, (b,), "grad")
+    _expect(grad, s, (b,), "grad")
     gs = torch.empty_like(s) if need_s else _empty0(s)
     gy = torch.empty_like(y) if need_y else _empty0(s)
     _cpu("bfgs_initial_scale_backward", s, b, n, N.ptr(s), N.ptr(y), N.ptr(grad), _cpu_ptr(gs if need_s else None),
@@ -1234,7 +1209,7 @@ def _(s, y, grad, need_s, need_y):
 @bfgs_scale_matrix.register_kernel("cpu")
 def _(scale, h):
     b, n = _square_batch(h)
-    _same(scale, h, (b,), "scale")
+    _expect(scale, h, (b,), "scale")
     out = torch.empty_like(h)
     _cpu("bfgs_scale_matrix", h, b, n, N.ptr(scale), N.ptr(h), N.ptr(out))
     return out
@@ -1243,7 +1218,7 @@ def _(scale, h):
 @bfgs_scale_matrix_backward.register_kernel("cpu")
 def _(scale, h, grad, need_scale, need_h):
     b, n = _square_batch(h)
-    _same(grad, h, (b, n, n), "grad")
+    _expect(grad, h, (b, n, n), "grad")
     gsc = torch.empty_like(scale) if need_scale else _empty0(h)
     gh = torch.empty_like(h) if need_h else _empty0(h)
     _cpu("bfgs_scale_matrix_backward", h, b, n, N.ptr(scale), N.ptr(h), N.ptr(grad),
@@ -1254,7 +1229,7 @@ def _(scale, h, grad, need_scale, need_h):
 @bfgs_search_direction.register_kernel("cpu")
 def _(h, g):
     b, n = _square_batch(h)
-    _same(g, h, (b, n), "gradient")
+    _expect(g, h, (b, n), "gradient")
     out = torch.empty_like(g)
     _cpu("bfgs_search_direction", h, b, n, N.ptr(h), N.ptr(g), N.ptr(out))
     return out
@@ -1263,7 +1238,7 @@ def _(h, g):
 @bfgs_search_direction_backward.register_kernel("cpu")
 def _(h, g, grad, need_h, need_g):
     b, n = _square_batch(h)
-    _same(grad, h, (b, n), "grad")
+    _expect(grad, h, (b, n), "grad")
     gh = torch.empty_like(h) if need_h else _empty0(h)
     gg = torch.empty_like(g) if need_g else _empty0(h)
     _cpu("bfgs_search_direction_backward", h, b, n, N.ptr(h), N.ptr(g), N.ptr(grad), _cpu_ptr(gh if need_h else None),
@@ -1274,8 +1249,8 @@ def _(h, g, grad, need_h, need_g):
 @wolfe_init.register_kernel("cpu")
 def _(direction, f0, g0):
     b, n = _row_batch(direction, "search_direction")
-    _same(g0, direction, (b, n), "base_gradient")
-    _same(f0, direction, (b,), "base_error")
+    _expect(g0, direction, (b, n), "base_gradient")
+    _expect(f0, direction, (b,), "base_error")
     state = direction.new_empty((b, WOLFE_STATE_COLUMNS))
     flags = direction.new_empty((b, WOLFE_FLAG_COLUMNS), dtype=torch.uint8)
     _cpu("wolfe_init", direction, b, n, N.ptr(direction), N.ptr(f0), N.ptr(g0), N.ptr(state), N.ptr(flags))
@@ -1310,7 +1285,7 @@ def l1_camera_evaluate(focal: Tensor, cx: Tensor, cy: Tensor, translation: Tenso
     for t, shape, what in ((cx, (b, e), "cx"), (cy, (b, e), "cy"), (translation, (b, e, m, 3), "translation"),
                            (lie, (b, e, m, 3), "orientation"), (world, (b, e, n - 2, 3), "world_points"),
                            (target, (b, m, n, 2), "true_projected_points")):
-        _same(t, focal, shape, what)
+        _expect(t, focal, shape, what)
     if tuple(visibility.shape) != (b, m, n) or visibility.dtype != torch.uint8 or not visibility.is_contiguous():
         raise ValueError("visibility must be a contiguous (B, M, N) uint8 tensor")
     err = focal.new_empty((b, e)) if want_error else _empty0(focal)
@@ -1347,11 +1322,11 @@ def l1_camera_vjp(focal: Tensor, cx: Tensor, cy: Tensor, translation: Tensor, li
     for t, shape, what in ((cx, (b, e), "cx"), (cy, (b, e), "cy"), (translation, (b, e, m, 3), "translation"),
                            (lie, (b, e, m, 3), "orientation"), (world, (b, e, n - 2, 3), "world_points"),
                            (target, (b, m, n, 2), "true_projected_points")):
-        _same(t, focal, shape, what)
+        _expect(t, focal, shape, what)
     if error_cotangent is not None:
-        _same(error_cotangent, focal, (b, e), "error cotangent")
+        _expect(error_cotangent, focal, (b, e), "error cotangent")
     if gradient_cotangent is not None:
-        _same(gradient_cotangent, focal, (b, e, p), "gradient cotangent")
+        _expect(gradient_cotangent, focal, (b, e, p), "gradient cotangent")
     if tuple(visibility.shape) != (b, m, n) or visibility.dtype != torch.uint8 or not visibility.is_contiguous():
         raise ValueError("visibility must be a contiguous (B, M, N) uint8 tensor")
     out = focal.new_zeros((b, e, 3 + 6 * m + 3 * (n - 2)))
@@ -1406,7 +1381,7 @@ def l1_camera_solve(focal: Tensor, cx: Tensor, cy: Tensor, translation: Tensor, 
     for t, shape, what in ((cx, (b, e), "cx"), (cy, (b, e), "cy"), (translation, (b, e, m, 3), "translation"),
                            (lie, (b, e, m, 3), "orientation"), (world, (b, e, n - 2, 3), "world_points"),
                            (target, (b, m, n, 2), "true_projected_points")):
-        _same(t, focal, shape, what)
+        _expect(t, focal, shape, what)
     if tuple(visibility.shape) != (b, m, n) or visibility.dtype != torch.uint8 or not visibility.is_contiguous():
         raise ValueError("visibility must be a contiguous (B, M, N) uint8 tensor")
     if max_iterations < 1 or widen_iterations < 0 or zoom_iterations < 0:
@@ -1451,151 +1426,6 @@ def _(focal, cx, cy, translation, lie, world, target, visibility, minimum_z_dist
     return (*[torch.empty_like(t) for t in (focal, cx, cy, translation, lie, world)], focal.new_empty((b, e)),
             focal.new_empty((b, e), dtype=torch.int32), focal.new_empty(tr), focal.new_empty(tr),
             focal.new_empty(tr, dtype=torch.int32))
-
-
-# ---------------------------------------- float64 fused gradient descent (SGDSolver) and its adjoint
-# One operator per operation: the C symbols take forms 0, 1 and 2 themselves (csrc/sgd_solve_f64.hip,
-# sgd_adjoint_f64.hip), with a workspace from torch's allocator sized by the library's host queries.
-
-def sgd_config_f64(learning_rate: float, iterations: int) -> N.DavaSgdConfigF64:
-    return N.DavaSgdConfigF64(float(learning_rate), int(iterations))
-
-
-def _sgd_scene_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                   distortion: bool, learning_rate: float, iterations: int, residual: int, what: str):
-    _require_float64(x0, what)
-    _check_scene_tensors(x0, observations, visibility, num_views, num_points, distortion)
-    if iterations < 0:
-        raise ValueError(f"iterations must be >= 0, got {iterations}")
-    sc = scene_struct_f64(observations, visibility, num_views, num_points, distortion, x0.shape[0], residual)
-    return sc, sgd_config_f64(learning_rate, iterations)
-
-
-_SGD_REFUSAL_F64 = ("this scene has no float64 fused gradient descent: more views than the view constants can hold "
-                    "in one workgroup's 160 KiB of LDS")
-_SGD_ADJOINT_REFUSAL_F64 = ("this scene has no float64 fused adjoint of the gradient descent: more views than the "
-                            "dual view constants can hold in one workgroup's 160 KiB of LDS")
-
-
-def _sgd_solve_workspace_f64(lib, sc, cfg, dev):
-    """(tensor, pointer, bytes) of the descent's workspace: form 2's vectors, or (None, None, 0)."""
-    if lib.dava_ba_sgd_solve_form_f64(sc, cfg) < 0:
-        raise ValueError(_SGD_REFUSAL_F64)
-    need = int(lib.dava_ba_sgd_solve_workspace_bytes_f64(sc, cfg))
-    if need == 0:
-        return None, None, 0
-    ws = _scratch(need, dev)
-    return ws, N.ptr(ws), ws.numel()
-
-
-@torch.library.custom_op("dava::ba_sgd_solve_f64", mutates_args=(), device_types=_CUDA)
-def ba_sgd_solve_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int, num_points: int,
-                     distortion: bool, learning_rate: float, iterations: int, residual: int,
-                     want_errors: bool) -> Tuple[Tensor, Tensor]:
-    """``dava_ba_sgd_solve_f64``: ``iterations`` steps x <- x - learning_rate dE/dx of a (B, P) float64 batch in
-    one launch, at any form.  Returns (x, E(x_k) (B, iterations) or empty)."""
-    lib = N.load_library()
-    sc, cfg = _sgd_scene_f64(x0, observations, visibility, num_views, num_points, distortion, learning_rate,
-                             iterations, residual, "the float64 fused gradient descent")
-    b, dev = x0.shape[0], x0.device
-    _ws, ws_ptr, ws_bytes = _sgd_solve_workspace_f64(lib, sc, cfg, dev)
-    x_out = torch.empty_like(x0)
-    errs = torch.empty((b, iterations), device=dev, dtype=torch.float64) if want_errors else _empty0(x0)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_sgd_solve_f64(sc, cfg, N.ptr(x0), N.ptr(x_out), N.ptr(errs) if want_errors else None,
-                                          ws_ptr, ws_bytes, N.stream_of(dev)), "dava_ba_sgd_solve_f64")
-    return x_out, errs
-
-
-@ba_sgd_solve_f64.register_fake
-def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
-      want_errors):
-    return torch.empty_like(x0), x0.new_empty((x0.shape[0], iterations) if want_errors else (0,))
-
-
-@torch.library.custom_op("dava::ba_sgd_solve_differentiable_f64", mutates_args=(), device_types=_CUDA)
-def ba_sgd_solve_differentiable_f64(x0: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
-                                    num_points: int, distortion: bool, learning_rate: float, iterations: int,
-                                    residual: int, want_errors: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """``dava_ba_sgd_solve_record_f64``: ``ba_sgd_solve_f64`` (bitwise its x and errors) that also writes the tape
-    (B, iterations, round_up(P, 4)) of x_k in float64.  An autograd node w.r.t. x0 and the observations: its backward
-    is ``ba_sgd_backward_f64`` (not differentiable twice).  Returns (x, errors or empty, tape)."""
-    lib = N.load_library()
-    sc, cfg = _sgd_scene_f64(x0, observations, visibility, num_views, num_points, distortion, learning_rate,
-                             iterations, residual, "the float64 recording gradient descent")
-    if lib.dava_ba_sgd_backward_form_f64(sc, cfg) < 0:
-        raise ValueError(_SGD_ADJOINT_REFUSAL_F64)
-    b, dev = x0.shape[0], x0.device
-    _ws, ws_ptr, ws_bytes = _sgd_solve_workspace_f64(lib, sc, cfg, dev)
-    tape = torch.empty((b, iterations, sgd_tape_rows(x0.shape[1])), device=dev, dtype=torch.float64)
-    if _POISON:
-        tape.fill_(float("nan"))
-    x_out = torch.empty_like(x0)
-    errs = torch.empty((b, iterations), device=dev, dtype=torch.float64) if want_errors else _empty0(x0)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_sgd_solve_record_f64(sc, cfg, N.ptr(x0), N.ptr(x_out),
-                                                 N.ptr(errs) if want_errors else None,
-                                                 N.ptr(tape) if tape.numel() else None, tape.numel() * 8, ws_ptr,
-                                                 ws_bytes, N.stream_of(dev)), "dava_ba_sgd_solve_record_f64")
-    return x_out, errs, tape
-
-
-@ba_sgd_solve_differentiable_f64.register_fake
-def _(x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
-      want_errors):
-    b = x0.shape[0]
-    return (torch.empty_like(x0), x0.new_empty((b, iterations) if want_errors else (0,)),
-            x0.new_empty((b, iterations, sgd_tape_rows(x0.shape[1]))))
-
-
-@torch.library.custom_op("dava::ba_sgd_backward_f64", mutates_args=(), device_types=_CUDA)
-def ba_sgd_backward_f64(x_out_grad: Tensor, tape: Tensor, observations: Tensor, visibility: Tensor, num_views: int,
-                        num_points: int, distortion: bool, learning_rate: float, iterations: int, residual: int,
-                        want_observations: bool) -> Tuple[Tensor, Tensor]:
-    """``dava_ba_sgd_backward_f64``: (dL/dx0, dL/dobs or empty) of a recorded float64 descent for dL/dx_out."""
-    lib = N.load_library()
-    sc, cfg = _sgd_scene_f64(x_out_grad, observations, visibility, num_views, num_points, distortion, learning_rate,
-                             iterations, residual, "the float64 gradient descent's adjoint")
-    b, dev = x_out_grad.shape[0], x_out_grad.device
-    rows = sgd_tape_rows(x_out_grad.shape[1])
-    # (the kernel dereferences the tape as device memory of this launch: refuse anything else loudly)
-    if (tape.device != dev or tape.dtype != torch.float64 or not tape.is_contiguous()
-            or tuple(tape.shape) != (b, iterations, rows)):
-        raise ValueError(f"tape must be the recording call's contiguous float64 ({b}, {iterations}, {rows}) tensor "
-                         f"on {dev}, got {tuple(tape.shape)} {tape.dtype} on {tape.device}")
-    if lib.dava_ba_sgd_backward_form_f64(sc, cfg) < 0:
-        raise ValueError(_SGD_ADJOINT_REFUSAL_F64)
-    need = int(lib.dava_ba_sgd_backward_workspace_bytes_f64(sc, cfg, 1 if want_observations else 0))
-    ws = _scratch(need, dev) if need else None
-    gx = torch.empty_like(x_out_grad)
-    gobs = torch.empty_like(observations) if want_observations else _empty0(x_out_grad)
-    with torch.cuda.device(dev):
-        N.check(lib.dava_ba_sgd_backward_f64(sc, cfg, N.ptr(tape) if tape.numel() else None, tape.numel() * 8,
-                                             N.ptr(x_out_grad), N.ptr(gx),
-                                             N.ptr(gobs) if want_observations else None, N.ptr(ws),
-                                             ws.numel() if need else 0, N.stream_of(dev)),
-                "dava_ba_sgd_backward_f64")
-    return gx, gobs
-
-
-@ba_sgd_backward_f64.register_fake
-def _(x_out_grad, tape, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
-      residual, want_observations):
-    return (torch.empty_like(x_out_grad),
-            torch.empty_like(observations) if want_observations else x_out_grad.new_empty((0,)))
-
-
-@torch.autograd.function.once_differentiable
-def _sgd_backward_f64(ctx, x_grad, _errors_grad, _tape_grad):
-    tape, observations, visibility = ctx.saved_tensors
-    need_x, need_obs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    x_grad = x_grad.to(torch.float64)
-    gx, gobs = ba_sgd_backward_f64(x_grad if x_grad.is_contiguous() else x_grad.contiguous(), tape,
-                                   observations.detach(), visibility, *ctx.meta, bool(need_obs))
-    return (gx if need_x else None, gobs if need_obs else None) + (None,) * 8
-
-
-ba_sgd_solve_differentiable_f64.register_autograd(_sgd_backward_f64, setup_context=_sgd_setup_context)
 
 
 OPS = ("bfgs_solve", "ba_solve", "ba_solve_record", "ba_solve_backward", "ba_evaluate", "ba_second_order",

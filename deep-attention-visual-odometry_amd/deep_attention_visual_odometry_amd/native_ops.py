@@ -12,7 +12,7 @@ import torch
 
 from . import _native as N
 from . import _ops  # (registers torch.ops.dava.*)
-from ._ops import _dt, scene_struct, solver_config
+from ._ops import _F32, _F64, _dt, scene_struct, scene_struct_f64, solver_config, solver_config_f64
 
 
 def _c(t: torch.Tensor) -> torch.Tensor:
@@ -34,6 +34,17 @@ def _fp32_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
     if x.dtype != torch.float32:
         raise TypeError("the fused BA kernels compute in float32 (the reference's BA dtype)")
     return _c(x.detach())
+
+
+def _f64_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
+    N.require_device_tensor(x, what)
+    if x.dtype != torch.float64:
+        raise TypeError(f"the float64 entry points take float64 tensors, got {x.dtype} for {what}")
+    return _c(x.detach())
+
+
+def _typed_on_device(x: torch.Tensor, what: str, dtype: torch.dtype) -> torch.Tensor:
+    return (_fp32_on_device if dtype == torch.float32 else _f64_on_device)(x, what)
 
 
 def _float_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
@@ -71,18 +82,19 @@ def ba_second_order(x: torch.Tensor, observations: torch.Tensor, visibility: tor
     """(E, dE/dx, H v + (d2E/dx dobs) u, dE/dobs, (d2E/dobs dx) v + (d2E/dobs2) u) for a (B, P) fp32 batch
     (``torch.ops.dava.ba_second_order``).  ``direction`` / ``obs_direction`` None mean v = 0 / u = 0 (with both
     None only E, dE/dx and dE/dobs are meaningful)."""
-    return _second_order_f32(torch.ops.dava.ba_second_order, x, observations, visibility, num_views, num_points,
-                             distortion, direction, residual, want_hv, want_obs, obs_direction)
+    return _second_order(torch.ops.dava.ba_second_order, torch.float32, x, observations, visibility, num_views,
+                         num_points, distortion, direction, residual, want_hv, want_obs, obs_direction)
 
 
-def _second_order_f32(op, x, observations, visibility, num_views, num_points, distortion, direction, residual,
-                      want_hv, want_obs, obs_direction):
-    x = _fp32_on_device(x, "x")
+def _second_order(op, dtype, x, observations, visibility, num_views, num_points, distortion, direction, residual,
+                  want_hv, want_obs, obs_direction):
+    """The body of the four second-derivative wrappers: ``op`` in ``dtype``."""
+    x = _typed_on_device(x, "x", dtype)
     obs, vis = _scene_inputs(x, observations, visibility)
     if obs_direction is not None:
-        obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=torch.float32)).reshape(obs.shape)
+        obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=dtype)).reshape(obs.shape)
     err, grad, hv, obs_grad, obs_hv = op(
-        x, obs, vis, num_views, num_points, bool(distortion), _opt(direction), int(residual), bool(want_hv),
+        x, obs, vis, num_views, num_points, bool(distortion), _opt(direction, dtype), int(residual), bool(want_hv),
         bool(want_obs), obs_direction)
     return (err, grad, hv if want_hv else None, obs_grad if want_obs else None,
             obs_hv if (want_obs and want_hv) else None)
@@ -106,28 +118,8 @@ def ba_second_order_large(x: torch.Tensor, observations: torch.Tensor, visibilit
     override, else that operator itself."""
     form0 = _ops.f32_old_symbol_runs(lambda: second_order_form(1, num_views, num_points, distortion, residual) == 0)
     op = torch.ops.dava.ba_second_order if form0 else torch.ops.dava.ba_second_order_large
-    return _second_order_f32(op, x, observations, visibility, num_views, num_points, distortion, direction, residual,
-                             want_hv, want_obs, obs_direction)
-
-
-def _f64_on_device(x: torch.Tensor, what: str) -> torch.Tensor:
-    N.require_device_tensor(x, what)
-    if x.dtype != torch.float64:
-        raise TypeError(f"the float64 entry points take float64 tensors, got {x.dtype} for {what}")
-    return _c(x.detach())
-
-
-def _second_order_f64(op, x, observations, visibility, num_views, num_points, distortion, direction, residual,
-                      want_hv, want_obs, obs_direction):
-    x = _f64_on_device(x, "x")
-    obs, vis = _scene_inputs(x, observations, visibility)
-    if obs_direction is not None:
-        obs_direction = _c(obs_direction.detach().to(device=x.device, dtype=torch.float64)).reshape(obs.shape)
-    err, grad, hv, obs_grad, obs_hv = op(
-        x, obs, vis, num_views, num_points, bool(distortion), _opt(direction, torch.float64), int(residual),
-        bool(want_hv), bool(want_obs), obs_direction)
-    return (err, grad, hv if want_hv else None, obs_grad if want_obs else None,
-            obs_hv if (want_obs and want_hv) else None)
+    return _second_order(op, torch.float32, x, observations, visibility, num_views, num_points, distortion, direction,
+                         residual, want_hv, want_obs, obs_direction)
 
 
 def ba_second_order_f64(x: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
@@ -136,8 +128,8 @@ def ba_second_order_f64(x: torch.Tensor, observations: torch.Tensor, visibility:
                         want_obs: bool = True, obs_direction: Optional[torch.Tensor] = None):
     """:func:`ba_second_order` for a (B, P) float64 batch with float64 observations
     (``torch.ops.dava.ba_second_order_f64``, dual numbers over double)."""
-    return _second_order_f64(torch.ops.dava.ba_second_order_f64, x, observations, visibility, num_views, num_points,
-                             distortion, direction, residual, want_hv, want_obs, obs_direction)
+    return _second_order(torch.ops.dava.ba_second_order_f64, torch.float64, x, observations, visibility, num_views,
+                         num_points, distortion, direction, residual, want_hv, want_obs, obs_direction)
 
 
 def second_order_form_f64(batch: int, num_views: int, num_points: int, distortion: bool,
@@ -145,8 +137,6 @@ def second_order_form_f64(batch: int, num_views: int, num_points: int, distortio
     """``dava_ba_second_order_form_f64`` (host-only): the form the float64 second derivatives take for this scene --
     0 the whole dual image in LDS (``dava_ba_second_order_f64``'s launch), 1 the scene read in place and the dual
     dE/dobs in a workspace, 2 the dual x and gradient there too -- or a negative value where they do not run."""
-    from ._ops import scene_struct_f64
-
     sc = scene_struct_f64(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
     return int(N.load_library().dava_ba_second_order_form_f64(sc))
 
@@ -160,8 +150,8 @@ def ba_second_order_large_f64(x: torch.Tensor, observations: torch.Tensor, visib
     override, else that operator itself."""
     form0 = _ops.f64_old_symbol_runs(lambda: second_order_form_f64(1, num_views, num_points, distortion, residual) == 0)
     op = torch.ops.dava.ba_second_order_f64 if form0 else torch.ops.dava.ba_second_order_large_f64
-    return _second_order_f64(op, x, observations, visibility, num_views, num_points, distortion, direction, residual,
-                             want_hv, want_obs, obs_direction)
+    return _second_order(op, torch.float64, x, observations, visibility, num_views, num_points, distortion, direction,
+                         residual, want_hv, want_obs, obs_direction)
 
 
 def ba_solve(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
@@ -274,17 +264,17 @@ def ba_solve_differentiable(x0: torch.Tensor, observations: torch.Tensor, visibi
     return _FusedSolve.apply(x0, observations, visibility, num_views, num_points, distortion, residual, cfg)
 
 
-def _sgd_query(name: str, batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
-               residual: int) -> int:
-    sc = scene_struct(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
-    return int(getattr(N.load_library(), name)(sc, _ops.sgd_config(0.0, iterations)))
+def _sgd_query(flavour, name: str, batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
+               residual: int, *more) -> int:
+    sc = flavour.scene(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
+    return int(getattr(N.load_library(), name)(sc, flavour.sgd_config(0.0, iterations), *more))
 
 
 def sgd_tape_bytes(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
                    residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
     """``dava_ba_sgd_tape_bytes`` (host-only): B * iterations * round_up(P, 4) * 4, or 0 where the fused gradient
     descent does not run this scene (and for ``iterations == 0``, which needs no tape)."""
-    return _sgd_query("dava_ba_sgd_tape_bytes", batch, num_views, num_points, distortion, iterations, residual)
+    return _sgd_query(_F32, "dava_ba_sgd_tape_bytes", batch, num_views, num_points, distortion, iterations, residual)
 
 
 def sgd_solve_supported(batch: int, num_views: int, num_points: int, distortion: bool,
@@ -296,7 +286,7 @@ def sgd_solve_supported(batch: int, num_views: int, num_points: int, distortion:
 def sgd_backward_supported(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
                            residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> bool:
     """``dava_ba_sgd_backward_supported`` (host-only): does the descent's adjoint kernel run this scene?"""
-    return _sgd_query("dava_ba_sgd_backward_supported", batch, num_views, num_points, distortion, iterations,
+    return _sgd_query(_F32, "dava_ba_sgd_backward_supported", batch, num_views, num_points, distortion, iterations,
                       residual) > 0
 
 
@@ -305,10 +295,16 @@ def ba_sgd_solve(x0: torch.Tensor, observations: torch.Tensor, visibility: torch
                  residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION, want_errors: bool = False):
     """``iterations`` steps of x <- x - learning_rate dE/dx for a (B, P) fp32 batch in one launch
     (``torch.ops.dava.ba_sgd_solve``).  Returns (x, E(x_k) (B, iterations) | None).  No graph."""
-    x0 = _fp32_on_device(x0, "parameters")
+    return _sgd_solve(torch.ops.dava.ba_sgd_solve, torch.float32, x0, observations, visibility, num_views, num_points,
+                      distortion, learning_rate, iterations, residual, want_errors)
+
+
+def _sgd_solve(op, dtype, x0, observations, visibility, num_views, num_points, distortion, learning_rate, iterations,
+               residual, want_errors):
+    x0 = _typed_on_device(x0, "parameters", dtype)
     obs, vis = _scene_inputs(x0, observations, visibility)
-    x, errs = torch.ops.dava.ba_sgd_solve(x0, obs, vis, int(num_views), int(num_points), bool(distortion),
-                                          float(learning_rate), int(iterations), int(residual), bool(want_errors))
+    x, errs = op(x0, obs, vis, int(num_views), int(num_points), bool(distortion), float(learning_rate),
+                 int(iterations), int(residual), bool(want_errors))
     return x, (errs if want_errors else None)
 
 
@@ -319,17 +315,21 @@ def ba_sgd_solve_differentiable(x0: torch.Tensor, observations: torch.Tensor, vi
     """The fused gradient descent as an autograd node w.r.t. x0 and the observations: the recording launch, and
     the adjoint kernel as its backward (``torch.ops.dava.ba_sgd_solve_differentiable``).  Returns (x, errors |
     None); the errors carry no graph."""
-    return _sgd_differentiable(torch.ops.dava.ba_sgd_solve_differentiable, x0, observations, visibility, num_views,
-                               num_points, distortion, learning_rate, iterations, residual, want_errors)
+    return _sgd_differentiable(torch.ops.dava.ba_sgd_solve_differentiable, torch.float32, x0, observations, visibility,
+                               num_views, num_points, distortion, learning_rate, iterations, residual, want_errors)
 
 
-def _sgd_differentiable(op, x0, observations, visibility, num_views, num_points, distortion, learning_rate,
+def _sgd_differentiable(op, dtype, x0, observations, visibility, num_views, num_points, distortion, learning_rate,
                         iterations, residual, want_errors):
     N.require_device_tensor(x0, "parameters")
-    if x0.dtype != torch.float32:
-        raise TypeError("the fused BA kernels compute in float32 (the reference's BA dtype)")
+    if dtype == torch.float32:
+        if x0.dtype != torch.float32:
+            raise TypeError("the fused BA kernels compute in float32 (the reference's BA dtype)")
+    elif x0.dtype != torch.float64 or observations.dtype != torch.float64:  # (float64 is never widened into)
+        raise TypeError(f"the float64 entry points take float64 tensors, got parameters {x0.dtype} and "
+                        f"observations {observations.dtype}")
     dev = x0.device
-    obs = _c(observations.to(device=dev, dtype=torch.float32))  # (kept in the graph)
+    obs = _c(observations.to(device=dev, dtype=dtype))  # (kept in the graph)
     vis = _c(visibility.detach().to(device=dev, dtype=torch.uint8))
     x, errs, _ = op(
         _c(x0), obs, vis, int(num_views), int(num_points), bool(distortion), float(learning_rate), int(iterations),
@@ -342,7 +342,8 @@ def sgd_backward_form(batch: int, num_views: int, num_points: int, distortion: b
     """``dava_ba_sgd_backward_form`` (host-only): the form the descent's adjoint takes for this scene -- 0
     ``dava_ba_sgd_backward``'s launch, 1 the scene read in place and the step's dual dE/dobs in a workspace, 2 the
     dual x and gradient there too -- or a negative value where it does not run."""
-    return _sgd_query("dava_ba_sgd_backward_form", batch, num_views, num_points, distortion, iterations, residual)
+    return _sgd_query(_F32, "dava_ba_sgd_backward_form", batch, num_views, num_points, distortion, iterations,
+                      residual)
 
 
 def ba_sgd_solve_differentiable_large(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor,
@@ -356,21 +357,16 @@ def ba_sgd_solve_differentiable_large(x0: torch.Tensor, observations: torch.Tens
     form0 = not torch.compiler.is_compiling() and _ops.f32_old_symbol_runs(
         lambda: sgd_backward_form(1, num_views, num_points, distortion, iterations, residual) == 0)
     op = torch.ops.dava.ba_sgd_solve_differentiable if form0 else torch.ops.dava.ba_sgd_solve_differentiable_large
-    return _sgd_differentiable(op, x0, observations, visibility, num_views, num_points, distortion, learning_rate,
-                               iterations, residual, want_errors)
-
-
-def _sgd_query_f64(name: str, batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
-                   residual: int, *more) -> int:
-    sc = _ops.scene_struct_f64(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
-    return int(getattr(N.load_library(), name)(sc, _ops.sgd_config_f64(0.0, iterations), *more))
+    return _sgd_differentiable(op, torch.float32, x0, observations, visibility, num_views, num_points, distortion,
+                               learning_rate, iterations, residual, want_errors)
 
 
 def sgd_tape_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
                        residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
     """``dava_ba_sgd_tape_bytes_f64`` (host-only): B * iterations * round_up(P, 4) * 8, or 0 where the float64 fused
     gradient descent does not run this scene (and for ``iterations == 0``, which needs no tape)."""
-    return _sgd_query_f64("dava_ba_sgd_tape_bytes_f64", batch, num_views, num_points, distortion, iterations, residual)
+    return _sgd_query(_F64, "dava_ba_sgd_tape_bytes_f64", batch, num_views, num_points, distortion, iterations,
+                      residual)
 
 
 def sgd_solve_form_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1,
@@ -378,7 +374,8 @@ def sgd_solve_form_f64(batch: int, num_views: int, num_points: int, distortion: 
     """``dava_ba_sgd_solve_form_f64`` (host-only): the form the float64 fused descent takes for this scene -- 0 the
     whole image in LDS, 1 the scene read in place, 2 x and the gradient in the workspace too -- or a negative value
     where it does not run."""
-    return _sgd_query_f64("dava_ba_sgd_solve_form_f64", batch, num_views, num_points, distortion, iterations, residual)
+    return _sgd_query(_F64, "dava_ba_sgd_solve_form_f64", batch, num_views, num_points, distortion, iterations,
+                      residual)
 
 
 def sgd_backward_form_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1,
@@ -386,23 +383,23 @@ def sgd_backward_form_f64(batch: int, num_views: int, num_points: int, distortio
     """``dava_ba_sgd_backward_form_f64`` (host-only): the form the float64 descent's adjoint takes -- 0 the dual
     image and the accumulator in LDS, 1 the scene read in place and the step's dual dE/dobs in a workspace, 2 the
     dual x and gradient there too -- or a negative value where it does not run.  Independent of the descent's form."""
-    return _sgd_query_f64("dava_ba_sgd_backward_form_f64", batch, num_views, num_points, distortion, iterations,
-                          residual)
+    return _sgd_query(_F64, "dava_ba_sgd_backward_form_f64", batch, num_views, num_points, distortion, iterations,
+                      residual)
 
 
 def sgd_solve_workspace_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1,
                                   residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
     """``dava_ba_sgd_solve_workspace_bytes_f64`` (host-only): form 2's vectors and the tail; 0 in forms 0 and 1."""
-    return _sgd_query_f64("dava_ba_sgd_solve_workspace_bytes_f64", batch, num_views, num_points, distortion,
-                          iterations, residual)
+    return _sgd_query(_F64, "dava_ba_sgd_solve_workspace_bytes_f64", batch, num_views, num_points, distortion,
+                      iterations, residual)
 
 
 def sgd_backward_workspace_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool,
                                      iterations: int = 1, residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION,
                                      observations_grad: bool = True) -> int:
     """``dava_ba_sgd_backward_workspace_bytes_f64`` (host-only)."""
-    return _sgd_query_f64("dava_ba_sgd_backward_workspace_bytes_f64", batch, num_views, num_points, distortion,
-                          iterations, residual, 1 if observations_grad else 0)
+    return _sgd_query(_F64, "dava_ba_sgd_backward_workspace_bytes_f64", batch, num_views, num_points, distortion,
+                      iterations, residual, 1 if observations_grad else 0)
 
 
 def ba_sgd_solve_f64(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor, num_views: int,
@@ -411,11 +408,8 @@ def ba_sgd_solve_f64(x0: torch.Tensor, observations: torch.Tensor, visibility: t
     """``iterations`` steps of x <- x - learning_rate dE/dx for a (B, P) float64 batch in one launch
     (``torch.ops.dava.ba_sgd_solve_f64``), at any scene size.  Returns (x, E(x_k) (B, iterations) | None).  No
     graph.  A float32 tensor raises ``TypeError``."""
-    x0 = _f64_on_device(x0, "parameters")
-    obs, vis = _scene_inputs(x0, observations, visibility)
-    x, errs = torch.ops.dava.ba_sgd_solve_f64(x0, obs, vis, int(num_views), int(num_points), bool(distortion),
-                                              float(learning_rate), int(iterations), int(residual), bool(want_errors))
-    return x, (errs if want_errors else None)
+    return _sgd_solve(torch.ops.dava.ba_sgd_solve_f64, torch.float64, x0, observations, visibility, num_views,
+                      num_points, distortion, learning_rate, iterations, residual, want_errors)
 
 
 def ba_sgd_solve_differentiable_f64(x0: torch.Tensor, observations: torch.Tensor, visibility: torch.Tensor,
@@ -425,16 +419,9 @@ def ba_sgd_solve_differentiable_f64(x0: torch.Tensor, observations: torch.Tensor
     """The float64 fused gradient descent as an autograd node w.r.t. x0 and the (float64) observations: the
     recording launch, and the adjoint kernel as its backward (``torch.ops.dava.ba_sgd_solve_differentiable_f64``).
     Returns (x, errors | None); the errors carry no graph.  A float32 tensor raises ``TypeError``."""
-    N.require_device_tensor(x0, "parameters")
-    if x0.dtype != torch.float64 or observations.dtype != torch.float64:
-        raise TypeError(f"the float64 entry points take float64 tensors, got parameters {x0.dtype} and "
-                        f"observations {observations.dtype}")
-    obs = _c(observations.to(device=x0.device))  # (kept in the graph)
-    vis = _c(visibility.detach().to(device=x0.device, dtype=torch.uint8))
-    x, errs, _ = torch.ops.dava.ba_sgd_solve_differentiable_f64(
-        _c(x0), obs, vis, int(num_views), int(num_points), bool(distortion), float(learning_rate), int(iterations),
-        int(residual), bool(want_errors))
-    return x, (errs.detach() if want_errors else None)
+    return _sgd_differentiable(torch.ops.dava.ba_sgd_solve_differentiable_f64, torch.float64, x0, observations,
+                               visibility, num_views, num_points, distortion, learning_rate, iterations, residual,
+                               want_errors)
 
 
 def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
@@ -442,8 +429,6 @@ def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distor
     """Host-only: does this shape have the float64 fused adjoint -- a recording forward
     (``dava_ba_solve_tape_bytes_f64`` > 0) AND a backward that can launch on it
     (``dava_ba_solve_backward_workspace_bytes_f64`` > 0)?"""
-    from ._ops import scene_struct_f64, solver_config_f64
-
     lib = N.load_library()
     sc = scene_struct_f64(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
     cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
@@ -453,8 +438,6 @@ def solve_tape_supported_f64(batch: int, num_views: int, num_points: int, distor
 
 def _f64_query(name: str, batch: int, num_views: int, num_points: int, distortion: bool, iterations: int,
                residual: int) -> int:
-    from ._ops import scene_struct_f64, solver_config_f64
-
     sc = scene_struct_f64(None, None, num_views, num_points, distortion, max(int(batch), 1), residual)
     cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
     return int(getattr(N.load_library(), name)(sc, cfg))
@@ -553,8 +536,6 @@ def solve_workspace_bytes(batch: int, num_views: int, num_points: int, distortio
 def solve_workspace_bytes_f64(batch: int, num_views: int, num_points: int, distortion: bool, iterations: int = 1000,
                               residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
     """``dava_ba_solve_workspace_bytes_f64`` (host-only): 0 where the float64 fused solve does not run."""
-    from ._ops import scene_struct_f64, solver_config_f64
-
     sc = scene_struct_f64(None, None, num_views, num_points, distortion, batch, residual)
     cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
     return int(N.load_library().dava_ba_solve_workspace_bytes_f64(sc, cfg))
@@ -565,8 +546,6 @@ def solve_form_f64(batch: int, num_views: int, num_points: int, distortion: bool
     """``dava_ba_solve_form_f64`` (host-only): the form the float64 fused solve takes for this scene -- 0 the whole
     image in LDS, 1 the scene read in place, 2 the vectors in the workspace too -- or a negative value where it
     does not run."""
-    from ._ops import scene_struct_f64, solver_config_f64
-
     sc = scene_struct_f64(None, None, num_views, num_points, distortion, batch, residual)
     cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
     return int(N.load_library().dava_ba_solve_form_f64(sc, cfg))
@@ -577,8 +556,6 @@ def solve_large_workspace_bytes_f64(batch: int, num_views: int, num_points: int,
                                     residual: int = N.DAVA_RESIDUAL_SQUARED_REPROJECTION) -> int:
     """``dava_ba_solve_large_workspace_bytes_f64`` (host-only): the history rows, in form 2 the vectors too;
     0 where the float64 fused solve does not run at any scene size."""
-    from ._ops import scene_struct_f64, solver_config_f64
-
     sc = scene_struct_f64(None, None, num_views, num_points, distortion, batch, residual)
     cfg = solver_config_f64(1e-4, 0.9, 1e-4, iterations, 1e-8, 1000, True)
     return int(N.load_library().dava_ba_solve_large_workspace_bytes_f64(sc, cfg))
