@@ -38,8 +38,6 @@
 namespace dava {
 namespace f64 {
 
-using Dual64 = DualT<double>;
-
 constexpr int kChunk = 32;      // rows per round of a pass (8 per wave)
 constexpr int kAdjVectors = 10;  // xb sbp gbp an db gk p1 p2 wb ak; s w y g_k share the dual vectors' 4 Pv
 

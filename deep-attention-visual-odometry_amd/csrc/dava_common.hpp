@@ -45,7 +45,14 @@ inline Layout make_layout(const DavaScene* s) {
   return Layout{s->num_views, s->num_points, s->num_parameters, s->distortion ? 1 : 0};
 }
 
+// A size whose images and workspace slices cannot be indexed in 32-bit offsets: refused by the descents, their
+// adjoints and the float32 second derivatives (far past any LDS image anyway).  check_scene must have passed.
+inline bool sizes_sane(const DavaScene& s) {
+  return (long long)s.num_views * s.num_points <= (1 << 24) && s.num_parameters <= (1 << 24);
+}
+
 constexpr int kMaxLds = 160 * 1024;  // one CU's LDS: the limit of every one-workgroup-per-problem image
+constexpr size_t kTailBytes = 256;   // ends every workspace with blocks: kept for a queue counter (none is used)
 
 // A launch with more than 64 KiB of dynamic LDS has to raise the kernel's limit first.
 template <typename Kernel>

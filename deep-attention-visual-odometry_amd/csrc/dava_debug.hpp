@@ -27,7 +27,7 @@ enum DebugKnob : int {
   kDbgGvScalarSlice,  // 0 | 1: GV wide pass's rho_j, c_j in LDS / in the workspace slice (default: by fit)
   kDbgAdjScGlobal,    // 0 | 1: LDS-mode adjoint's tape scalar row staged in LDS / read in place (default: by fit)
   kDbgF64Form,        // 1 | 2: raises the float64 kernels' form (solve_f64.hpp) above the one the fit chooses
-  kDbgF32DualForm,    // 1 | 2: raises the float32 dual-number kernels' form (ba_second_carve.hpp) above the fit's
+  kDbgF32DualForm,    // 1 | 2: raises the float32 dual-number kernels' form (dual_image.hpp) above the fit's
   kDbgL1SolveForm,    // 1: raises the fused legacy solve's form (camera_l1_solve.hip) above the fit's
   kDbgKnobs
 };

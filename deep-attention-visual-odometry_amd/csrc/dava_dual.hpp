@@ -8,8 +8,8 @@
 // differentiating THROUGH a solve needs from the objective (the reference gets
 // it from autograd's double backward, bfgs_solver.py:133-135 create_graph).
 //
-// The dual number is generic in its real type: Dual = DualT<float> for the fp32 kernels,
-// DualT<double> for the float64 second derivatives and adjoint (ba_second_order_f64.hip,
+// The dual number is generic in its real type: Dual = DualT<float> for the fp32 kernels, Dual64 =
+// DualT<double> for the float64 ones (ba_second_order.hpp and sgd_adjoint.hpp instantiate both;
 // bfgs_adjoint_f64.hip).
 #pragma once
 
@@ -85,6 +85,7 @@ struct DualT {
   friend __device__ __forceinline__ bool operator==(DualT a, DualT b) { return a.v == b.v; }
 };
 using Dual = DualT<float>;
+using Dual64 = DualT<double>;
 
 // The real type a scalar is built on: float for float and Dual, double for double and DualT<double>.  Step
 // sizes, observations, reduction scratch and constants of the objective code have this type.

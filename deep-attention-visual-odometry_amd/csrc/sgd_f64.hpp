@@ -1,5 +1,5 @@
-// What the float64 gradient descent (sgd_solve_f64.hip) and its adjoint (sgd_adjoint_f64.hip) share: the config
-// check, the tape, and the update's arithmetic.
+// What the float64 gradient descent (sgd_solve_f64.hip) and its adjoint (sgd_adjoint.hpp, through dual_image.hpp)
+// share: the config check, the tape, and the update's arithmetic.
 #pragma once
 
 #include "ba_objective.hpp"
@@ -18,11 +18,6 @@ __device__ __forceinline__ double descend(double a, double lr, double b) {
 
 inline int sgd_config_status(const DavaSgdConfigF64* c) {
   return !c || c->iterations < 0 ? DAVA_ERR_INVALID_ARGUMENT : DAVA_OK;
-}
-
-// (a size whose images and slices cannot be indexed in 32-bit offsets is refused: far past any image anyway)
-inline bool sgd_sizes_sane(const DavaScene& s) {
-  return (long long)s.num_views * s.num_points <= (1 << 24) && s.num_parameters <= (1 << 24);
 }
 
 // The tape: x_k for k = 0 .. K-1, rows of Pv = round_up(P, 4) doubles, laid out (B, K, Pv) in every form.  No header.

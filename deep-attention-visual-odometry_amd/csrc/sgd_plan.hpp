@@ -1,9 +1,10 @@
-// The geometry of the fused gradient descent (sgd_solve.hip) and of its adjoint (sgd_adjoint.hip): the LDS
-// images, the tape, and -- host only -- what the entry points and the size queries derive from
-// (scene, config).  The kernels index their LDS with the same code the host sizes it with.
+// The geometry of the float32 fused gradient descent (sgd_solve.hip): the LDS image, the tape its adjoint
+// (sgd_adjoint.hpp) replays, and -- host only -- what the entry points and the size queries derive from
+// (scene, config).  The kernels index their LDS with the same code the host sizes it with.  The adjoint's image
+// is the dual one of dual_image.hpp, followed by dual_acc_bytes of accumulator.
 #pragma once
 
-#include "ba_second_carve.hpp"
+#include "dual_image.hpp"
 #include "solve_plan.hpp"
 
 namespace dava {
@@ -31,11 +32,6 @@ __host__ __device__ inline SgdCarve carve_sgd(int M, int N, int Pv, bool gv, int
 // The tape: x_k for k = 0 .. K-1, rows of Pv = round_up(P, 4) floats, laid out (B, K, Pv).  No header.
 inline size_t sgd_tape_bytes(int B, int K, int Pv) { return (size_t)B * (size_t)K * (size_t)Pv * sizeof(float); }
 
-// Adjoint image: carve_second's (dual x and gradient, dual view constants and partials, dual dE/dobs, scratch,
-// observations, visibility) followed by the float accumulator of dL/dobs (2 M N floats).
-__host__ __device__ inline int sgd_adjoint_acc_bytes_off(const SecondCarve& c) { return c.total_bytes; }
-inline int sgd_adjoint_acc_bytes(int M, int N) { return round_up(2 * M * N, 4) * 4; }
-
 // ---- host only ----
 struct SgdPlan {
   int status;  // DAVA_OK, or why no launch runs (then the other fields are unset)
@@ -43,11 +39,6 @@ struct SgdPlan {
   bool ppt;    // LDS form with a point per thread in registers
   int Pv, lds_bytes;
 };
-
-// (a size whose images cannot be carved in 32-bit offsets is far past LDS anyway)
-inline bool sgd_sizes_sane(const DavaScene* s) {
-  return (long long)s->num_views * s->num_points <= (1 << 24) && s->num_parameters <= (1 << 24);
-}
 
 // check_scene(scene, ...) must have passed.
 inline SgdPlan plan_sgd(const DavaScene* scene, const DavaSgdConfig* config) {
@@ -57,7 +48,7 @@ inline SgdPlan plan_sgd(const DavaScene* scene, const DavaSgdConfig* config) {
     return p;
   }
   p.status = DAVA_ERR_UNSUPPORTED;
-  if (!sgd_sizes_sane(scene)) return p;
+  if (!sizes_sane(*scene)) return p;
   const EvalPlan e = plan_eval(scene);  // the evaluation's form; the image is the descent's own
   p.gv = e.gv;
   p.ppt = e.ppt;

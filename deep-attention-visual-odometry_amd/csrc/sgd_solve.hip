@@ -10,7 +10,7 @@
 //                     sweep, eight waves -- the evaluate kernel's GV + XL form without the direction slot.
 // A step is ba_eval<GRAD> (which ends on a barrier and overwrites every gradient entry: nothing to re-zero),
 // the update, and one barrier.  The update rounds as torch does: the product first, then the difference.
-// RECORD also writes x_k, k = 0 .. K-1, to the tape (B, K, Pv) the adjoint replays (sgd_adjoint.hip); it
+// RECORD also writes x_k, k = 0 .. K-1, to the tape (B, K, Pv) the adjoint replays (sgd_adjoint.hpp); it
 // changes no arithmetic, so a recording launch returns bitwise the plain launch's x_out and error trace.
 #include <hip/hip_runtime.h>
 

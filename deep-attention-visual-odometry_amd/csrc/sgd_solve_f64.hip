@@ -8,7 +8,7 @@
 // In every form the view constants, the per-wave view partials and the two reduction buffers are in LDS.
 // A step is f64::eval<GRAD> (which ends on a barrier and overwrites every gradient entry), the update -- the
 // product rounded, then the difference, as torch does in float64 -- and one barrier.  RECORD also writes x_k,
-// k = 0 .. K-1, to the tape (B, K, Pv) the adjoint replays (sgd_adjoint_f64.hip); it changes no arithmetic.
+// k = 0 .. K-1, to the tape (B, K, Pv) the adjoint replays (sgd_adjoint.hpp); it changes no arithmetic.
 // Host side: one plan and one launcher for the plain and the recording entry point (dava_f64.hpp's rule); both plan
 // with any_form = true -- there is no symbol of the LDS image alone.
 #include "sgd_f64.hpp"
@@ -134,7 +134,7 @@ inline SgdShape sgd_shape(const DavaScene& sc, const DavaSgdConfigF64* c) {
   s.status = sgd_config_status(c);
   if (s.status != DAVA_OK) return s;
   s.status = DAVA_ERR_UNSUPPORTED;
-  if (!sgd_sizes_sane(sc)) return s;
+  if (!sizes_sane(sc)) return s;
   s.Pv = round_up(sc.num_parameters, 4);
   s.form = choose_sgd_form(sc.num_views, sc.num_points, s.Pv);
   if (s.form < 0) return s;

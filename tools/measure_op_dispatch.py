@@ -1,9 +1,12 @@
-"""Per-call time of three ``torch.ops.dava`` operators at the smallest scene, this tree against another checkout of
-the package (the parent commit, built), to see what a change of the operator layer in ``_ops.py`` costs per call.
+"""Per-call time of ``torch.ops.dava`` operators, this tree against another checkout of the package (the parent
+commit, built), to see what a change of the operator layer in ``_ops.py`` -- or of a kernel whose code object did not
+come out identical -- costs per call.
 
-  ba_sgd_solve, ba_sgd_backward_f64, ba_second_order_large at B = 3, 2 views, 16 points, K = 1
+  ba_sgd_solve, ba_sgd_backward_f64, ba_second_order_large, ba_sgd_backward_large at B = 3, 2 views, 16 points, K = 1
+  ba_second_order_large, ba_sgd_backward_large, ba_second_order_large_f64, ba_sgd_backward_f64 at B = 3, 2 views,
+  3600 points, K = 1 (names ending in @2x3600): the dual-number kernels in form 2
 
-At this size a call is bound by the dispatch and the launch, not by the kernel.  Two checkouts register the same
+At the small size a call is bound by the dispatch and the launch, not by the kernel.  Two checkouts register the same
 operator names, so they cannot share a process: the trees alternate process by process, in both orders (other, this,
 this, other, ...), `--rounds` processes each.  A process warms every operator up, then times `--batches` batches of `--calls`
 calls each with a host clock around the batch, ended by a device synchronise, and reports the median batch as
@@ -23,7 +26,9 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OPS = ("ba_sgd_solve", "ba_sgd_backward_f64", "ba_second_order_large")
+OPS = ("ba_sgd_solve", "ba_sgd_backward_f64", "ba_second_order_large", "ba_sgd_backward_large",
+       "ba_second_order_large@2x3600", "ba_sgd_backward_large@2x3600", "ba_second_order_large_f64@2x3600",
+       "ba_sgd_backward_f64@2x3600")
 
 
 def child(tree: str, batches: int, calls: int) -> None:
@@ -34,20 +39,28 @@ def child(tree: str, batches: int, calls: int) -> None:
 
     assert torch.cuda.is_available(), "needs a ROCm device"
     dev = torch.device("cuda", 0)
-    m, n, k, lr = 2, 16, 1, 1e-4
-    s = make_scenes(3, m, n, distortion=False, seed=7)
-    x = torch.tensor(s.initial, dtype=torch.float32, device=dev)
-    obs = torch.tensor(s.observations, dtype=torch.float32, device=dev)
-    vis = torch.tensor(s.visibility, dtype=torch.uint8, device=dev)
-    x64, obs64 = x.double(), obs.double()
-    _, _, tape64 = torch.ops.dava.ba_sgd_solve_differentiable_f64(x64, obs64, vis, m, n, False, lr, k, 0, False)
-    cot64 = torch.ones_like(x64)
+    k, lr = 1, 1e-4
     ops = torch.ops.dava
-    fns = {
-        "ba_sgd_solve": lambda: ops.ba_sgd_solve(x, obs, vis, m, n, False, lr, k, 0, False),
-        "ba_sgd_backward_f64": lambda: ops.ba_sgd_backward_f64(cot64, tape64, obs64, vis, m, n, False, lr, k, 0, True),
-        "ba_second_order_large": lambda: ops.ba_second_order_large(x, obs, vis, m, n, False, None, 0, True, True, None),
-    }
+    def scene_fns(m, n):
+        s = make_scenes(3, m, n, distortion=False, seed=7)
+        x = torch.tensor(s.initial, dtype=torch.float32, device=dev)
+        obs = torch.tensor(s.observations, dtype=torch.float32, device=dev)
+        vis = torch.tensor(s.visibility, dtype=torch.uint8, device=dev)
+        x64, obs64 = x.double(), obs.double()
+        _, _, tape = ops.ba_sgd_solve_differentiable_large(x, obs, vis, m, n, False, lr, k, 0, False)
+        _, _, tape64 = ops.ba_sgd_solve_differentiable_f64(x64, obs64, vis, m, n, False, lr, k, 0, False)
+        cot, cot64 = torch.ones_like(x), torch.ones_like(x64)
+        return {
+            "ba_sgd_solve": lambda: ops.ba_sgd_solve(x, obs, vis, m, n, False, lr, k, 0, False),
+            "ba_sgd_backward_f64": lambda: ops.ba_sgd_backward_f64(cot64, tape64, obs64, vis, m, n, False, lr, k, 0, True),
+            "ba_second_order_large": lambda: ops.ba_second_order_large(x, obs, vis, m, n, False, None, 0, True, True, None),
+            "ba_sgd_backward_large": lambda: ops.ba_sgd_backward_large(cot, tape, obs, vis, m, n, False, lr, k, 0, True),
+            "ba_second_order_large_f64": lambda: ops.ba_second_order_large_f64(x64, obs64, vis, m, n, False, None, 0, True,
+                                                                               True, None),
+        }
+
+    fns = scene_fns(2, 16)
+    fns.update({name + "@2x3600": fn for name, fn in scene_fns(2, 3600).items()})
     out = {}
     for name in OPS:
         fn = fns[name]
@@ -92,7 +105,8 @@ def main() -> None:
     for i in range(args.rounds):
         for which in (("other", "this") if i % 2 == 0 else ("this", "other")):
             rounds[which].append(run_child(other if which == "other" else REPO, args))
-    line = {"tool": "measure_op_dispatch", "scene": "B=3, 2 views x 16 points, K=1", "unit": "us per call",
+            print(f"round {i + 1}/{args.rounds} {which}: done", file=sys.stderr, flush=True)
+    line = {"tool": "measure_op_dispatch", "scene": "B=3, 2 views x 16 points (@2x3600: x 3600 points), K=1", "unit": "us per call",
             "rounds": args.rounds, "batches": args.batches, "calls": args.calls, "ops": {}}
     for name in OPS:
         o = [r[name] for r in rounds["other"]]
