@@ -1,8 +1,13 @@
 """HIP objective kernel (dava_ba_evaluate) vs the oracle / reference goldens.
 
 fp32 tolerances: error and gradient are compared normwise against an fp64
-oracle evaluation of the same fp32 inputs; the kernel's reductions run in a
-different order than torch's, so agreement is at the ~1e-6 level.
+oracle evaluation of the same fp32 inputs, over the whole vector: E rtol 2e-5,
+gradient 1e-4, slope rtol 1e-3.  The kernel's reductions run in a different
+order than torch's; the whole-vector norm is dominated by the intrinsics and
+rotation blocks (the point and translation blocks are 1/100 to 1/1000 of it),
+so the two oracle tests also hold every block to the bars of tests/f32_bars.py,
+which come from the float32 oracle's own error (a few 1e-6 per block).  Edge
+shapes, forms and flavours: tests/test_gpu_objective_edges.py.
 """
 import os
 
@@ -10,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import f32_bars
 from conftest import GOLDEN
 from oracle import objective
 
@@ -53,6 +59,17 @@ def test_error_gradient_and_slope_match_oracle(device, shape, distortion):
     rel = (g - g_ref).norm(dim=-1) / g_ref.norm(dim=-1)
     assert rel.max() < 1e-4, rel
     assert torch.allclose(sl, sl_ref, rtol=1e-3, atol=1e-5 * g_ref.norm(dim=-1).max().item())
+    _per_block(f"{shape}_{'bc' if distortion else 'pinhole'}", "bc" if distortion else "pinhole", m, n, x, obs, vis, d,
+               e, g, sl)
+
+
+def _per_block(case, model, m, n, x, obs, vis, d, e, g, sl):
+    """The same launch per block of the parameter vector, against bars from the oracle's own float32 error."""
+    reference = f32_bars.reference_at(model, m, n, x, obs, vis, d)
+    tally = f32_bars.Tally("objective_shapes", case)
+    tally.add("110", reference, f32_bars.measure_evaluation(reference, e, g, sl))
+    failures = tally.emit()
+    assert not failures, failures
 
 
 @pytest.mark.parametrize("distortion", [False, True])
@@ -191,6 +208,7 @@ def test_ray_angle_error_gradient_and_slope_match_oracle(device, shape):
     rel = (g - g_ref).norm(dim=-1) / g_ref.norm(dim=-1)
     assert rel.max() < 1e-4, rel
     assert torch.allclose(sl, sl_ref, rtol=1e-3, atol=1e-5 * g_ref.norm(dim=-1).max().item())
+    _per_block(f"{shape}_ray", "ray", m, n, x, obs, vis, d, e, g, sl)
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))

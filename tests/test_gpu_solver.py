@@ -455,6 +455,14 @@ def test_c5_shape_objective_matches_oracle(device):
     assert ((g.cpu().double() - g_ref).norm(dim=-1) / g_ref.norm(dim=-1)).max() < 1e-4
     sl_ref = (g_ref * d.double()).sum(-1)
     assert torch.allclose(sl.cpu().double(), sl_ref, rtol=1e-3, atol=1e-6 * g_ref.norm().item())
+    # the all-pairs packed sweep, per block of the parameter vector (bars from the float32 oracle's own error)
+    import f32_bars
+
+    reference = f32_bars.reference_at("pinhole", 16, 4096, x, obs, vis, d)
+    tally = f32_bars.Tally("c5", "m16_n4096")
+    tally.add("110", reference, f32_bars.measure_evaluation(reference, e.cpu(), g.cpu(), sl.cpu()))
+    failures = tally.emit()
+    assert not failures, failures
 
 
 @pytest.mark.parametrize("xl", [True, False])
